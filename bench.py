@@ -89,7 +89,13 @@ def main():
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI) or gloo (rehearsal)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy: "
+                         "output_ids (float64) and pred_masks_<b> (f32 mask logits of image b), at most 64 MB in all "
+                         "(beyond that a fixed, seeded sample of each image's logits + its flat indices)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -125,7 +131,29 @@ def main():
     def family(tag):
         return "_".join(tag.split("_")[:2])              # gemv_bf16_swiglu_x8 -> gemv_bf16
 
-    def measure(config, steps, warmup, B=None, mode=None, roofline_steps=3, stamps_out=None, full=True):
+    def dump_outputs(out_dir, oids, masks, budget=64_000_000):
+        """What a caller of the timed path received in the last timed step -> out_dir/<name>.npy (f32 / f64).  Inputs and
+        weights are seeded, so two builds run with the same arguments can be compared file for file."""
+        import numpy as np
+        os.makedirs(out_dir, exist_ok=True)
+        files = {"output_ids": oids.cpu().double().numpy()}       # int64 ids < 2^53: exact in float64
+        masks = [] if masks is None else [m.detach().float().cpu() for m in masks]
+        room = (budget - files["output_ids"].nbytes - (64 << 10)) // 4   # float32 mask elements that fit (64 KiB: npy headers)
+        fits = sum(m.numel() for m in masks) <= room
+        per_image = room // max(1, len(masks))
+        for b, m in enumerate(masks):
+            if fits or m.numel() <= per_image:
+                files[f"pred_masks_{b}"] = m.numpy()
+            else:                                                # f32 value + f64 flat index: 3 elements' room each
+                idx = torch.randperm(m.numel(), generator=torch.Generator().manual_seed(b))[: per_image // 3].sort().values
+                files[f"pred_masks_{b}_sample"] = m.reshape(-1)[idx].numpy()
+                files[f"pred_masks_{b}_sample_index"] = idx.double().numpy()
+        for name, a in files.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        log(f"[bench] outputs of the last timed step -> {out_dir}: " +
+            ", ".join(f"{k} {list(v.shape)} {v.dtype}" for k, v in files.items()))
+
+    def measure(config, steps, warmup, B=None, mode=None, roofline_steps=3, stamps_out=None, full=True, dump_dir=None):
         """Build `config`, time `steps` steps of it on the production path, then (untimed) measure its dominant
         kernel.  -> (result dict, context for the CPU / parity legs)."""
         mode = mode or args.mode or ("perf_fp8w" if config == "c5" else "perf")
@@ -189,9 +217,12 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            last = step()
         barrier()
         dt = time.perf_counter() - t0
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, *last)
+        del last
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         if world > 1:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -441,7 +472,7 @@ def main():
         return res, ctx
 
     res, ctx = measure(args.config, args.steps, args.warmup, B=args.batch_per_gpu, roofline_steps=args.roofline_steps,
-                       stamps_out=args.stamps_out)
+                       stamps_out=args.stamps_out, dump_dir=args.dump_outputs)
     if args.config in ("c4", "c5", "c3"):
         args.no_cpu_baseline = True      # the CPU baseline / parity legs are quoted on C2 (13B fp32 needs ~55 GB of host memory)
     cfg, sd, model, clip, sam, ids, sizes, H, W = (ctx[k] for k in ("cfg", "sd", "model", "clip", "sam", "ids", "sizes", "H", "W"))
