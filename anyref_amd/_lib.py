@@ -98,6 +98,11 @@ SYMBOLS = {
     "anyref_op_kaldi_fbank": (_I, [_P, _P, _I, _I, _I, _I, _I, C.c_float, _P, _I, _P, _P, _I, C.c_float, C.c_float, _P]),
     "anyref_op_clip_finish": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
     "anyref_op_gemv": (_I, [_I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "anyref_op_gemv_xn": (_I, [_I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I]),
+    "anyref_op_rope_table": (_I, [_I, _I, _F, _P]),
+    "anyref_op_decode_attn": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _I]),
+    "anyref_op_rope_cache": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "anyref_op_argmax": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_norm": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _F, _I]),
     "anyref_op_attention": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _I, _I]),
     "anyref_op_attention_tab": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _I, _I]),

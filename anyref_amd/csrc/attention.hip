@@ -1556,6 +1556,27 @@ template bool launch_decode_attn<float>(const float*, int, int, int, const int*,
 template bool launch_decode_attn<bf16>(const float*, int, int, int, const int*, const float*, void*, void*, int, float,
                                        float*, void*, hipStream_t);
 
+template <typename T>
+void launch_decode_step_attn(const float* qkv, int B, int H, int hd, const int* pos, const int* kv_len, const float* cs_tab,
+                             void* q_tmp, void* kc, void* vc, int maxS, float scale, float* out, void* q_keep, hipStream_t s,
+                             bool force_fallback) {
+  if (!force_fallback && launch_decode_attn<T>(qkv, B, H, hd, pos, cs_tab, kc, vc, maxS, scale, out, q_keep, s)) return;
+  launch_rope_cache_f32<T>(qkv, B, H, hd, pos, cs_tab, q_tmp, kc, vc, maxS, q_keep, s);
+  AttnArgs a;
+  a.Q = q_tmp; a.K = kc; a.V = vc; a.O = out; a.o_f32 = 1;
+  a.q_bs = H * hd; a.q_rs = H * hd; a.q_hs = hd;
+  a.k_bs = a.v_bs = (int64_t)maxS * H * hd; a.k_rs = a.v_rs = H * hd; a.k_hs = a.v_hs = hd;
+  a.o_bs = H * hd; a.o_rs = H * hd; a.o_hs = hd;
+  a.B = B; a.H = H; a.Sq = 1; a.Sk = maxS; a.hd = hd;
+  a.scale = scale;
+  a.kv_len = kv_len;
+  launch_attention<T>(a, s);
+}
+template void launch_decode_step_attn<float>(const float*, int, int, int, const int*, const int*, const float*, void*, void*,
+                                             void*, int, float, float*, void*, hipStream_t, bool);
+template void launch_decode_step_attn<bf16>(const float*, int, int, int, const int*, const int*, const float*, void*, void*,
+                                            void*, int, float, float*, void*, hipStream_t, bool);
+
 // ---------------------------------------------------------------------------------------------
 // Head-mean attention row of one query (rephrase branch).  One workgroup per batch element.
 // ---------------------------------------------------------------------------------------------

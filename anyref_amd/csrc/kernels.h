@@ -292,6 +292,12 @@ bool attention_takes_rel_tables(int elem_bytes, int hd, int Sq, int Sk, int kh, 
 template <typename T>
 bool launch_decode_attn(const float* qkv, int B, int H, int hd, const int* pos, const float* cs_tab, void* kc,
                         void* vc, int maxS, float scale, float* out, void* q_keep, hipStream_t s);
+// The decode step's attention as llm_decode_step runs it: launch_decode_attn, or where it refuses (or force_fallback)
+// launch_rope_cache_f32 into q_tmp T [B,H*hd] + the generic attention kernel with Sq = 1 over kv_len[b] = pos[b] + 1 keys
+template <typename T>
+void launch_decode_step_attn(const float* qkv, int B, int H, int hd, const int* pos, const int* kv_len, const float* cs_tab,
+                             void* q_tmp, void* kc, void* vc, int maxS, float scale, float* out, void* q_keep, hipStream_t s,
+                             bool force_fallback = false);
 
 // Head-mean softmax row of ONE query per batch element over keys [0, kv_len):
 // out[b, j] = mean_h softmax_j(scale * q[b,h].k[b,j,h])   (anyref.py:748-749)
@@ -356,6 +362,8 @@ void launch_rope_cache(const void* qkv, int B, int S, int H, int hd, const int* 
 template <typename T>
 void launch_rope_cache_f32(const float* qkv, int B, int H, int hd, const int* pos, const float* cs_tab,
                            void* q_out, void* kc, void* vc, int maxS, void* q_keep, hipStream_t s);
+// cos | sin table [S][2][hd/2] of pos * theta^(-2d/hd) in HF LlamaRotaryEmbedding's fp32 op order (host memory)
+void rope_table(int S, int hd, float theta, float* out);
 // token embedding rows for the decode step: x[b,:] = table[ids[b],:]
 void launch_embed_rows(const int64_t* ids, int B, const void* table, int is_bf16, int D, float* x, hipStream_t s);
 // row_map[b] = b*maxS + pos[b]; kvlen[b] = pos[b] + 1

@@ -766,13 +766,7 @@ void Model<T, TS>::finalize() {
     }
     // rotary table, same fp32 op order as HF LlamaRotaryEmbedding
     std::vector<float> tab((size_t)S * hd);
-    for (int pos = 0; pos < S; ++pos)
-      for (int d = 0; d < hd / 2; ++d) {
-        const float inv = 1.0f / powf(c.llm_rope_theta, (float)(2 * d) / (float)hd);
-        const float fr = (float)pos * inv;
-        tab[((size_t)pos * 2) * (hd / 2) + d] = cosf(fr);
-        tab[((size_t)pos * 2 + 1) * (hd / 2) + d] = sinf(fr);
-      }
+    rope_table(S, hd, c.llm_rope_theta, tab.data());
     rope_tab_ = upload_f32(tab);
     cache_layer_stride_ = (size_t)MB * S * H;
     kcache_ = talloc<Q>(cache_layer_stride_ * c.llm_layers);
@@ -1366,19 +1360,8 @@ void Model<T, TS>::llm_decode_step(hipStream_t s, int B, bool keep_q) {
       launch_gemv<T>(g, s);
     }
     Q* qk = (keep_q && i == nl - 1) ? q_last_ : nullptr;
-    if (!launch_decode_attn<Q>(d_qkv_, B, nh, hd, pos_dev_, rope_tab_, kc, vc, S, 1.f / sqrtf((float)hd), d_att_, qk,
-                               s)) {
-      launch_rope_cache_f32<Q>(d_qkv_, B, nh, hd, pos_dev_, rope_tab_, d_q_, kc, vc, S, qk, s);
-      AttnArgs a;
-      a.Q = d_q_; a.K = kc; a.V = vc; a.O = d_att_; a.o_f32 = 1;
-      a.q_bs = H; a.q_rs = H; a.q_hs = hd;
-      a.k_bs = a.v_bs = (int64_t)S * H; a.k_rs = a.v_rs = H; a.k_hs = a.v_hs = hd;
-      a.o_bs = H; a.o_rs = H; a.o_hs = hd;
-      a.B = B; a.H = nh; a.Sq = 1; a.Sk = S; a.hd = hd;
-      a.scale = 1.f / sqrtf((float)hd);
-      a.kv_len = kvlen_dev_;
-      launch_attention<Q>(a, s);
-    }
+    launch_decode_step_attn<Q>(d_qkv_, B, nh, hd, pos_dev_, kvlen_dev_, rope_tab_, d_q_, kc, vc, S, 1.f / sqrtf((float)hd),
+                               d_att_, qk, s);
     if (mfma_decode) {
       launch_convert<T>(d_att_, H, l_att_, apad<T>(H), B, H, s);
       if (!gemm(s, l_att_, H, L.o, d_x_, H, B, ACT_NONE, true, d_x_, H, nullptr, &L.post_norm, l_h_))

@@ -905,6 +905,16 @@ void launch_rope_cache_f32(const float* qkv, int B, int H, int hd, const int* po
                      cs_tab, reinterpret_cast<T*>(q_out), reinterpret_cast<T*>(kc), reinterpret_cast<T*>(vc),
                      maxS, reinterpret_cast<T*>(q_keep));
 }
+// cos | sin table [S][2][hd/2] of the rotary embedding, same fp32 op order as HF LlamaRotaryEmbedding (host)
+void rope_table(int S, int hd, float theta, float* out) {
+  for (int pos = 0; pos < S; ++pos)
+    for (int d = 0; d < hd / 2; ++d) {
+      const float inv = 1.0f / powf(theta, (float)(2 * d) / (float)hd);
+      const float fr = (float)pos * inv;
+      out[((size_t)pos * 2) * (hd / 2) + d] = cosf(fr);
+      out[((size_t)pos * 2 + 1) * (hd / 2) + d] = sinf(fr);
+    }
+}
 template void launch_rope_cache_f32<float>(const float*, int, int, int, const int*, const float*, void*, void*,
                                            void*, int, void*, hipStream_t);
 template void launch_rope_cache_f32<bf16>(const float*, int, int, int, const int*, const float*, void*, void*,
@@ -976,7 +986,18 @@ template void launch_swiglu<bf16>(const void*, int, int, void*, hipStream_t);
 // workgroup per row, 16-byte loads all issued before the first compare (the row is read once, the
 // kernel is pure latency); `bump` (optional) is a per-row counter incremented by one -- the decode
 // step's position -- so the step needs no separate increment launch.
+// NaN counts as the greatest value (torch.argmax returns the first NaN of a row), so every row -- all NaN, all -inf --
+// ends on an index in [0, N); the order (NaN first, then value, then the smaller index) is total, so the lane /
+// wave reductions below give the same index in any combination order.
 __device__ __forceinline__ void argmax_take(float v, int i, float& best, int& bi) {
+  const bool vn = __builtin_isnan(v), bn = __builtin_isnan(best);
+  if (vn || bn) {
+    if (vn && (!bn || i < bi)) {
+      best = v;
+      bi = i;
+    }
+    return;
+  }
   if (v > best || (v == best && i < bi)) {
     best = v;
     bi = i;

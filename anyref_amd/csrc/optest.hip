@@ -85,6 +85,69 @@ int anyref_op_gemv(int t, void* stream, const float* x, const float* gain, float
   });
 }
 
+int anyref_op_gemv_xn(int t, void* stream, const float* x, const float* gain, float eps, const void* W, const void* W2,
+                      const float* bias, float* y, const float* resid, int B, int N, int K, int act, float* xn_out,
+                      const int32_t* xn_row_map, int xn_ld) {
+  OP_GUARD({
+    GemvArgs a;
+    a.x = x; a.ldx = K; a.gain = gain; a.eps = eps; a.W = W; a.W2 = W2; a.bias = bias; a.y = y; a.resid = resid;
+    a.ldy = N; a.B = B; a.N = N; a.K = K; a.act = act;
+    a.xn_out = xn_out; a.xn_row_map = xn_row_map; a.xn_ld = xn_ld;
+    if (t == 0) launch_gemv<float>(a, (hipStream_t)stream);
+    else if (t == 1) launch_gemv<bf16>(a, (hipStream_t)stream);
+    else throw std::runtime_error("op_gemv_xn: t = 0 / 1");
+  });
+}
+
+int anyref_op_rope_table(int S, int hd, float theta, float* out_host) { OP_GUARD(rope_table(S, hd, theta, out_host)); }
+
+int anyref_op_decode_attn(int t, void* stream, const float* qkv, int B, int H, int hd, const int32_t* pos,
+                          const float* cs_tab, void* kc, void* vc, int maxS, float scale, float* out, void* q_keep,
+                          int force_fallback) {
+  OP_GUARD({
+    if (t != 0 && t != 1) throw std::runtime_error("op_decode_attn: t = 0 / 1");
+    hipStream_t st = (hipStream_t)stream;
+    // kv_len[b] = pos[b] + 1 (the model's kvlen_dev_, written by the argmax of the step before)
+    std::vector<int> h(B);
+    HIP_TRY(hipMemcpy(h.data(), pos, (size_t)B * 4, hipMemcpyDeviceToHost));
+    for (int& v : h) v += 1;
+    TmpBuf kv_len((size_t)B * 4);
+    TmpBuf q_tmp((size_t)B * H * hd * 4);
+    HIP_TRY(hipMemcpy(kv_len.p, h.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    if (t == 0)
+      launch_decode_step_attn<float>(qkv, B, H, hd, pos, (const int*)kv_len.p, cs_tab, q_tmp.p, kc, vc, maxS, scale, out,
+                                     q_keep, st, force_fallback != 0);
+    else
+      launch_decode_step_attn<bf16>(qkv, B, H, hd, pos, (const int*)kv_len.p, cs_tab, q_tmp.p, kc, vc, maxS, scale, out,
+                                    q_keep, st, force_fallback != 0);
+  });
+}
+
+int anyref_op_rope_cache(int t, void* stream, const void* qkv, const float* slab0, const float* slab1, int B, int S, int H,
+                         int hd, const int32_t* pos0, const int32_t* lens, const float* cs_tab, void* q_out, void* kc,
+                         void* vc, int maxS, void* q_keep) {
+  OP_GUARD({
+    hipStream_t st = (hipStream_t)stream;
+    if (t != 0 && t != 1) throw std::runtime_error("op_rope_cache: t = 0 / 1");
+    if (slab0)
+      launch_rope_cache_slabs(slab0, slab1, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st, t == 0);
+    else if (t == 0)
+      launch_rope_cache<float>(qkv, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st);
+    else
+      launch_rope_cache<bf16>(qkv, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st);
+  });
+}
+
+int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_t* out, int32_t* pos, const void* table,
+                     int is_bf16, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen) {
+  OP_GUARD({
+    if (table)
+      launch_argmax_next(x, M, N, ldx, out, pos, table, is_bf16, D, maxS, x_next, row_map, kvlen, (hipStream_t)stream);
+    else
+      launch_argmax(x, M, N, ldx, out, (hipStream_t)stream, pos);
+  });
+}
+
 int anyref_op_norm(int t, void* stream, const float* x, const float* gain, const float* bias, float* y, int M,
                    int D, float eps, int rms) {
   OP_GUARD({
