@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(HERE, "libanyref_hip.so")
 
 ABI_VERSION = 2
 F32, BF16, F16 = 0, 1, 2
-MODE_PARITY, MODE_PERF, MODE_PERF_FP8W, MODE_PARITY16 = 0, 1, 2, 3
+MODE_PARITY, MODE_PERF, MODE_PERF_FP8W, MODE_PARITY16, MODE_PERF_F16 = 0, 1, 2, 3, 4
 
 
 class AnyrefConfig(C.Structure):
@@ -85,6 +85,7 @@ SYMBOLS = {
     "anyref_stamps_spread": (_I, [_P, _L, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "anyref_device_bytes": (_L, [_P]),
     "anyref_mode_name": (C.c_char_p, [_P]),
+    "anyref_inexact_weights": (_I, [_P, C.POINTER(_L)]),
     # kernel-level test entry points (anyref_hip_ops.h)
     "anyref_op_gemm": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "anyref_op_gemm_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),

@@ -210,6 +210,13 @@ int anyref_stamps_spread(anyref_handle* h, int64_t idx, double* start_spread_us,
 
 int64_t anyref_device_bytes(anyref_handle* h) { return h && h->m ? h->m->device_bytes() : 0; }
 
+int anyref_inexact_weights(anyref_handle* h, int64_t* out) {
+  GUARD(h, {
+    if (!out) throw std::runtime_error("anyref_inexact_weights: out is NULL");
+    *out = h->m->inexact_weights();
+  });
+}
+
 const char* anyref_mode_name(anyref_handle* h) { return h && h->m ? h->m->mode_name() : ""; }
 
 }  // extern "C"

@@ -1538,7 +1538,8 @@ bool launch_decode_attn(const float* qkv, int B, int H, int hd, const int* pos, 
     constexpr int HD = decltype(tagHD)::value;
     const size_t lds = decode_attn_lds<T, HD>(maxS);
     const double kvbytes = 2.0 * B * H * HD * sizeof(T) * (maxS / 2);  // nominal: half-full cache
-    ProfScope prof(sizeof(T) == 2 ? "decode_attn_bf16" : "decode_attn_f32", 0.0, kvbytes, s);
+    ProfScope prof(is_half16<T>::value ? "decode_attn_f16" : sizeof(T) == 2 ? "decode_attn_bf16" : "decode_attn_f32", 0.0,
+                   kvbytes, s);
     hipLaunchKernelGGL((decode_attn_kernel<T, HD>), dim3(H, B), dim3(512), lds, s, qkv, pos, cs_tab,
                        reinterpret_cast<T*>(kc), reinterpret_cast<T*>(vc), maxS, H, scale, out,
                        reinterpret_cast<T*>(q_keep));
@@ -1555,6 +1556,8 @@ template bool launch_decode_attn<float>(const float*, int, int, int, const int*,
                                         float*, void*, hipStream_t);
 template bool launch_decode_attn<bf16>(const float*, int, int, int, const int*, const float*, void*, void*, int, float,
                                        float*, void*, hipStream_t);
+template bool launch_decode_attn<f16>(const float*, int, int, int, const int*, const float*, void*, void*, int, float,
+                                      float*, void*, hipStream_t);
 
 template <typename T>
 void launch_decode_step_attn(const float* qkv, int B, int H, int hd, const int* pos, const int* kv_len, const float* cs_tab,
@@ -1576,6 +1579,8 @@ template void launch_decode_step_attn<float>(const float*, int, int, int, const 
                                              void*, int, float, float*, void*, hipStream_t, bool);
 template void launch_decode_step_attn<bf16>(const float*, int, int, int, const int*, const int*, const float*, void*, void*,
                                             void*, int, float, float*, void*, hipStream_t, bool);
+template void launch_decode_step_attn<f16>(const float*, int, int, int, const int*, const int*, const float*, void*, void*,
+                                           void*, int, float, float*, void*, hipStream_t, bool);
 
 // ---------------------------------------------------------------------------------------------
 // Head-mean attention row of one query (rephrase branch).  One workgroup per batch element.
@@ -1640,6 +1645,8 @@ template void launch_attn_row_mean<float>(const void*, int64_t, int64_t, const v
                                           const int*, int, int, int, float, float*, int, hipStream_t);
 template void launch_attn_row_mean<bf16>(const void*, int64_t, int64_t, const void*, int64_t, int64_t, int64_t,
                                          const int*, int, int, int, float, float*, int, hipStream_t);
+template void launch_attn_row_mean<f16>(const void*, int64_t, int64_t, const void*, int64_t, int64_t, int64_t,
+                                        const int*, int, int, int, float, float*, int, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // SAM decomposed relative-position bias tables (image_encoder.py:354-392; get_rel_pos with

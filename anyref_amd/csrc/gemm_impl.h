@@ -1106,7 +1106,7 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
         go(I128(), I160(), I4(), I2(), I3(), "gemm_bf16_128x160s3");  // SAM fc2: 32 x 8 tiles = one per CU
         return;
       }
-      if constexpr (!is_half16<T>::value) {  // the LLaMA prefill / CLIP shapes (bf16 only: not compiled for the f16 towers)
+      {  // the LLaMA prefill / CLIP shapes (bf16, and f16 in ANYREF_MODE_PERF_F16)
         if (!a.w_fp8 && knobs().m320 >= 0 && a.M > 192 && a.M <= 320 && a.N >= 16384 && a.batch == 1 && cdiv(a.N, 96) <= cus) {
           // prefill gate/up (320 x 22016 x 4096): every workgroup owns a weight panel outright (all of M in one
           // tile, 230 panels on 256 CUs) instead of five 64-row workgroups sharing one: 7 % faster from cold weights
@@ -1147,7 +1147,7 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
           return;
         }
       }
-      if constexpr (!is_half16<T>::value) {
+      {
         // CLIP qkv / fc1 (257 x 3072 / 4096 x 1024): 72 / 96 workgroups of 128^2 stream 32 KB per K tile each through L2 -> LDS
         // (~0.5 us x 16 K tiles + ~4 us of launch, first tile and epilogue); 64 x 128 tiles are 120 / 160 workgroups at 24 KB
         static const bool clip64 = !(getenv("ANYREF_GEMM_CLIP64") && atoi(getenv("ANYREF_GEMM_CLIP64")) == 0);

@@ -39,7 +39,7 @@ static int gemv_grid_knob() {
 constexpr bool NO_DOT2 = ANYREF_GEMV_NO_DOT2;
 template <typename T, int NB, bool DUAL, int XPT, bool W8 = false, bool PAIR = false>  // XPT: x elements per thread in registers, K <= 512 * XPT
 __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
-  static_assert(!W8 || sizeof(T) == 2, "fp8 weights go with bf16 activations");
+  static_assert(!W8 || std::is_same<T, bf16>::value, "fp8 weights go with bf16 activations");
   // T = sp16 (ANYREF_MODE_PARITY16): bf16 weights, exactly as stored, against the f32 activation row kept in LDS as f32
   // (16 - 44 KB) -- same bytes per decode step as the bf16 mode, f32 products and sums
   using WE = std::conditional_t<is_split<T>::value, bf16, T>;   // weight element
@@ -52,9 +52,9 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
   // workgroup fits beside a resident 256^2 GEMM workgroup of the co-running SAM stream) measured equal within
   // noise, alone and under the overlap
   constexpr int UNR = 4;
-  // packed bf16 dot products (v_dot2c_f32_bf16) for every batch size of the bf16 mode, batch 1 included; the f32 and the
-  // split-pair (sp16) builds keep the unpack + f32 FMA chain
-  constexpr bool DOT2 = std::is_same<T, bf16>::value && !W8 && !NO_DOT2;
+  // packed 16-bit dot products (v_dot2c_f32_bf16 / v_dot2c_f32_f16) for every batch size of the bf16 and f16 modes, batch 1
+  // included; the f32 and the split-pair (sp16) builds keep the unpack + f32 FMA chain
+  constexpr bool DOT2 = (std::is_same<T, bf16>::value || is_half16<T>::value) && !W8 && !NO_DOT2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   XE* xs = reinterpret_cast<XE*>(smem);  // [NB][K]
   __shared__ float red[NB][8];
@@ -213,6 +213,7 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
           // rows per pass the unpack + FMA form keeps the VALU ~60 % busy and the step is no longer HBM-bound
           // (decode step at batch 4: 4.1 ms against 2.9 ms at batch 1)
           typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+          typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
           uint4v xv[NB];
 #pragma unroll
           for (int b = 0; b < NB; ++b)
@@ -224,8 +225,12 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
 #pragma unroll
               for (int j = 0; j < 4; ++j) {
                 const uint32_t wj = wcur[u][r][j], xj = xv[b][j];
-                acc[r][b] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, wj), __builtin_bit_cast(bf16x2, xj),
-                                                            acc[r][b], false);
+                if constexpr (is_half16<T>::value)
+                  acc[r][b] = __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, wj), __builtin_bit_cast(f16x2, xj), acc[r][b],
+                                                     false);
+                else
+                  acc[r][b] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, wj), __builtin_bit_cast(bf16x2, xj),
+                                                              acc[r][b], false);
               }
         } else {
         float xf[NB][VN];
@@ -693,7 +698,8 @@ static void gemv_dispatch(const GemvArgs& a_in, int b0, int nb, hipStream_t s) {
     const double wbytes = (double)a.N * a.K * wsz * (a.W2 ? 2 : 1) + (double)nb * (a.K + a.N) * 4;
     // one tag per kernel instantiation, so a tag's average can be checked against rocprofv3's per-kernel one
     char tag[40];
-    snprintf(tag, sizeof(tag), "gemv_%s%s_x%d", a.w_fp8 ? "fp8w" : (is_split<T>::value ? "sp16" : sizeof(T) == 2 ? "bf16" : "f32"),
+    snprintf(tag, sizeof(tag), "gemv_%s%s_x%d",
+             a.w_fp8 ? "fp8w" : (is_split<T>::value ? "sp16" : is_half16<T>::value ? "f16" : sizeof(T) == 2 ? "bf16" : "f32"),
              a.W2 ? "_swiglu" : "", XPT);
     ProfScope prof(tag, 2.0 * nb * a.N * (double)a.K * (a.W2 ? 2 : 1), wbytes, s);
     if (g_stamp && g_stamp->on) a.stamp = g_stamp->slot(tag, wbytes, grid);
@@ -714,7 +720,7 @@ static void gemv_dispatch(const GemvArgs& a_in, int b0, int nb, hipStream_t s) {
       if (pair) launch(dual_t, w8_t, TT());
       else launch(dual_t, w8_t, FF());
     };
-    if constexpr (sizeof(T) == 2) {
+    if constexpr (std::is_same<T, bf16>::value) {
       if (a.w_fp8) {
         if (a.W2) by_pair(TT(), TT());
         else by_pair(FF(), TT());
@@ -738,7 +744,7 @@ template <typename T>
 void launch_gemv(const GemvArgs& a, hipStream_t s) {
   const int VN = a.w_fp8 ? 16 : Vec16<std::conditional_t<is_split<T>::value, bf16, T>>::N;
   if (a.K % VN || ((uintptr_t)a.W & 15)) throw std::runtime_error("gemv: K must be a multiple of 16 bytes");
-  if (a.w_fp8 && (sizeof(T) != 2 || !a.wscale || (a.W2 && !a.wscale2)))
+  if (a.w_fp8 && (!std::is_same<T, bf16>::value || !a.wscale || (a.W2 && !a.wscale2)))
     throw std::runtime_error("gemv: fp8 weights need the bf16 mode and per-row scales");
   if (((uintptr_t)a.x & 15) || a.ldx % 4 || a.K % 4 || (a.gain && ((uintptr_t)a.gain & 15)) ||
       (a.xn_out && (((uintptr_t)a.xn_out & 15) || a.xn_ld % 4)))
@@ -791,5 +797,6 @@ void launch_gemv_skinny_f32(const GemvArgs& a, hipStream_t s) {
 }
 template void launch_gemv<bf16>(const GemvArgs&, hipStream_t);
 template void launch_gemv<sp16>(const GemvArgs&, hipStream_t);
+template void launch_gemv<f16>(const GemvArgs&, hipStream_t);
 
 }  // namespace anyref

@@ -202,8 +202,9 @@ void launch_gemv(const GemvArgs& a, hipStream_t s);
 void launch_gemv_skinny_f32(const GemvArgs& a, hipStream_t s);
 // Row-wise fp8 (e4m3fn) weight quantisation: scale[n] = max|W[n,:]| / 448 (1 if the row is zero),
 // q[n,k] = RNE_e4m3(W[n,k] / scale[n]); src f32 [N, K] (row stride lds), q [N, K] bytes (row stride ldq)
+// inexact (optional, device): += elements with q * scale != W
 void launch_quant_fp8_rows(const float* src, int lds, int N, int K, uint8_t* q, int ldq, float* scale, hipStream_t s,
-                           int scale_stride = 1);
+                           int scale_stride = 1, unsigned long long* inexact = nullptr);
 // q * scale -> bf16 [N, K] (prefill GEMM operand)
 void launch_dequant_fp8_rows(const uint8_t* q, int ldq, const float* scale, int N, int K, void* out_bf16, int ldo,
                              hipStream_t s);
@@ -320,10 +321,11 @@ void launch_im2col_patch(const float* img, int B, int S, int p, void* out, int K
 // 3x3 pad-1 im2col on NHWC tokens: in T [B,g,g,C] -> out T [B*g*g, 9*C], k = (ky*3+kx)*C + c
 template <typename T>
 void launch_im2col_3x3(const void* in, int B, int g, int C, void* out, hipStream_t s);
-// generic f32 -> T convert / copy with strides (rows x cols)
+// generic f32 -> T convert / copy with strides (rows x cols).  counts (optional, device, 16-bit T; weight packing):
+// counts[0] += elements whose stored value differs (float(T(x)) != x), counts[1] += finite elements stored as inf
 template <typename T>
 void launch_convert(const float* in, int64_t ld_in, void* out, int64_t ld_out, int rows, int cols,
-                    hipStream_t s);
+                    hipStream_t s, unsigned long long* counts = nullptr);
 // split-pair (sp16) rows -> f32: out[r, c] = hi + lo; ld_in in sp16 elements (a multiple of 64)
 void launch_unsplit(const void* in, int64_t ld_in, float* out, int64_t ld_out, int rows, int cols, hipStream_t s);
 // out[m, :] = a[m, :] + b[m % bmod, :]   (f32; position embeddings, keys+pe ...)
@@ -340,19 +342,21 @@ void launch_l2norm_scale(const float* x, int rows, int D, float scale, float* y,
 // token embedding gather + multimodal splice (LLaVA prepare_inputs; see oracle.splice_embeddings)
 // ids i64 dev [B,Lmax], lens i32 dev [B]; image placeholder (-200) expands to n_img rows of img_feat[b].
 // extra rows replace 1:1.  x f32 [B,Smax,D]; out_len i32 dev [B] (= len + n_img - 1 when an image is present).
+// emb_dtype: 0 = f32, 1 = bf16, 2 = f16 table
 void launch_embed_splice(const int64_t* ids, const int* lens, int B, int Lmax, const void* emb_table,
-                         int emb_is_bf16, int vocab, const float* img_feat, int n_img, float* x, int Smax,
+                         int emb_dtype, int vocab, const float* img_feat, int n_img, float* x, int Smax,
                          int D, int* out_len, hipStream_t s);
 void launch_scatter_rows(const float* rows, const int* dst_b, const int* dst_pos, int n, float* x, int Smax,
                          int D, hipStream_t s);
 // RoPE (rotate_half form) on q,k of a fused qkv buffer + append k,v to the cache.
 // qkv T [B,S,3,H,hd]; pos0 i32 [B] dev; q_out T [B,S,H,hd]; kc/vc T [B,maxS,H,hd];
 // cs_tab f32 [maxS][2][hd/2] = cos | sin of pos * inv_freq (built on the host like HF does)
-// same from two f32 split-K slices of the projection (slab0 + slab1, rounded to bf16 first like the GEMM's own output);
-// out_f32: q_out / kc / vc / q_keep are f32 and the sum is not rounded (ANYREF_MODE_PARITY16)
+// same from two f32 split-K slices of the projection (slab0 + slab1, rounded to T first like the GEMM's own output, T = bf16 /
+// f16); T = float: q_out / kc / vc / q_keep are f32 and the sum is not rounded (ANYREF_MODE_PARITY16)
+template <typename T>
 void launch_rope_cache_slabs(const float* slab0, const float* slab1, int B, int S, int H, int hd, const int* pos0,
                              const int* lens, const float* cs_tab, void* q_out, void* kc, void* vc, int maxS, void* q_keep,
-                             hipStream_t s, bool out_f32 = false);
+                             hipStream_t s);
 template <typename T>
 void launch_rope_cache(const void* qkv, int B, int S, int H, int hd, const int* pos0, const int* lens,
                        const float* cs_tab, void* q_out, void* kc, void* vc, int maxS, void* q_keep,
@@ -365,7 +369,7 @@ void launch_rope_cache_f32(const float* qkv, int B, int H, int hd, const int* po
 // cos | sin table [S][2][hd/2] of pos * theta^(-2d/hd) in HF LlamaRotaryEmbedding's fp32 op order (host memory)
 void rope_table(int S, int hd, float theta, float* out);
 // token embedding rows for the decode step: x[b,:] = table[ids[b],:]
-void launch_embed_rows(const int64_t* ids, int B, const void* table, int is_bf16, int D, float* x, hipStream_t s);
+void launch_embed_rows(const int64_t* ids, int B, const void* table, int dtype, int D, float* x, hipStream_t s);
 // row_map[b] = b*maxS + pos[b]; kvlen[b] = pos[b] + 1
 void launch_decode_index(const int* pos, int B, int maxS, int* row_map, int* kvlen, hipStream_t s);
 // tokens[i, 0:n_out] = out_tokens; tokens[i, n_out] = pred[i]   (mask_decoder.py:127-141)
@@ -377,8 +381,8 @@ void launch_swiglu(const void* gu, int M, int F, void* out, hipStream_t s);
 // argmax over f32 rows (first index on ties) -> i64
 void launch_argmax(const float* x, int M, int N, int ldx, int64_t* out, hipStream_t s, int* bump = nullptr);
 // argmax, pos[b] += 1, and the next decode step's inputs in the same launch: x_next[b] = table[argmax], row_map[b] =
-// b * maxS + pos[b], kvlen[b] = pos[b] + 1
-void launch_argmax_next(const float* x, int M, int N, int ldx, int64_t* out, int* pos, const void* table, int is_bf16,
+// b * maxS + pos[b], kvlen[b] = pos[b] + 1; table dtype 0 = f32, 1 = bf16, 2 = f16
+void launch_argmax_next(const float* x, int M, int N, int ldx, int64_t* out, int* pos, const void* table, int dtype,
                         int D, int maxS, float* x_next, int* row_map, int* kvlen, hipStream_t s);
 // ConvTranspose2d k2s2 output un-shuffle (+ LayerNorm2d + GELU): tmp f32 [n*g*g, 4*C] (col = (dy*2+dx)*C+c)
 // -> out T [n*(2g)*(2g), C] NHWC

@@ -58,6 +58,11 @@ class ModelBase {
                         float* out_low) = 0;
 
   int64_t device_bytes() const { return bytes_; }
+  // weight elements held in a value other than the one handed to set_weight (16-bit / fp8 packing at finalize)
+  int64_t inexact_weights() const {
+    if (!finalized_) throw std::runtime_error("inexact_weights before finalize");
+    return inexact_;
+  }
   void set_seg_range(int lo, int hi) {
     cfg.seg_lo = lo;
     cfg.seg_hi = hi;
@@ -98,6 +103,12 @@ class ModelBase {
   std::unordered_map<void*, size_t> allocs_;
   std::map<std::string, RawTensor> raw_;
   bool finalized_ = false;
+  // counts of the weight packing (launch_convert / launch_quant_fp8_rows): [0] inexact elements, [1] finite elements stored as
+  // inf; a plain hipMalloc for the length of finalize (not in device_bytes), summed into inexact_ at its end
+  unsigned long long* wcount_ = nullptr;
+  unsigned long long* weight_counts();
+  void close_weight_counts();
+  int64_t inexact_ = 0;
   bool overlap_ = true;
   bool use_graphs_ = true;
   int side_wgs_ = getenv("ANYREF_SIDE_WGS") ? atoi(getenv("ANYREF_SIDE_WGS")) : 128;

@@ -29,6 +29,23 @@ ModelBase::~ModelBase() {
   (void)hipSetDevice(device_);
   (void)hipDeviceSynchronize();
   for (auto& kv : allocs_) (void)hipFree(kv.first);
+  if (wcount_) (void)hipFree(wcount_);
+}
+
+unsigned long long* ModelBase::weight_counts() {
+  if (!wcount_) {
+    HIP_TRY(hipMalloc(&wcount_, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(wcount_, 0, 2 * sizeof(unsigned long long)));
+  }
+  return wcount_;
+}
+void ModelBase::close_weight_counts() {
+  if (!wcount_) return;
+  unsigned long long h[2] = {0, 0};
+  HIP_TRY(hipMemcpy(h, wcount_, sizeof(h), hipMemcpyDeviceToHost));
+  inexact_ += (int64_t)h[0];
+  (void)hipFree(wcount_);
+  wcount_ = nullptr;
 }
 
 void* ModelBase::dalloc(size_t bytes) {
@@ -132,7 +149,7 @@ struct Affine {
   float* b = nullptr;
 };
 
-// T: storage type of the LLaMA / CLIP / audio operands (float: parity, bf16: perf).  TS: storage type of the SAM image
+// T: storage type of the LLaMA / CLIP / audio operands (float: parity, bf16: perf, f16: perf_f16).  TS: storage type of the SAM image
 // encoder's operands -- f16 in the perf build: per-stage attribution on the parity workload (tests/test_gpu_c2_full.py,
 // DESIGN.md §3) puts 3.8e-2 of the bf16 build's 3.7e-2 mask-logit error in this tower alone (CLIP 2.4e-3, LLaMA 8e-3);
 // f16 has 3 more mantissa bits at the same MFMA rate and bytes, and is what the reference runs it in
@@ -156,7 +173,7 @@ class Model : public ModelBase {
   }
   Model(const anyref_config& c, int device) : ModelBase(c, device) {
     fp8w_ = c.mode == ANYREF_MODE_PERF_FP8W;
-    if (fp8w_ && sizeof(T) != 2) throw std::runtime_error("fp8 weights need the bf16 compute mode");
+    if (fp8w_ && !std::is_same<T, bf16>::value) throw std::runtime_error("fp8 weights need the bf16 compute mode");
     // the split-pair encoder is twice as long as the 16-bit one: spread over 8 decode steps instead of 6
     // (scratch/side_share.py, parity16 at C2: 49.2 - 49.9 ms with 6, 48.3 - 48.6 with 8 - 10; caps other than 128 lose 1 - 10 ms)
     if (SPS && !getenv("ANYREF_SIDE_STEPS")) side_steps_ = 8;
@@ -184,6 +201,7 @@ class Model : public ModelBase {
   }
   const char* mode_name() const override {
     if (SPT) return "f32 activations as bf16 pairs x bf16 weights";
+    if (is_half16<T>::value) return "f16";
     return sizeof(T) == 2 ? (fp8w_ ? (is_half16<TS>::value ? "bf16+fp8w, SAM f16" : "bf16+fp8w")
                                    : (is_half16<TS>::value ? "bf16, SAM f16" : "bf16"))
                           : "f32";
@@ -220,6 +238,7 @@ class Model : public ModelBase {
   std::vector<float> to_host(const std::string& name);
   template <typename E>
   E* pack_rows(E* dst, int dst_row0, const std::string& name, int rows, int cols, int kpad);
+  void check_f16_range(const std::string& name);
   template <typename E = W>
   Lin<E> pack_linear(const std::string& wname, const std::string& bname, int n, int k, int kalign = 8,
                      int rowpad = 0);
@@ -304,6 +323,8 @@ class Model : public ModelBase {
       g.W2 = l.w + (size_t)row0 * l.stride();
     }
   }
+  // dtype code of the embedding table (packed as W) for the embed / argmax kernels: 0 = f32, 1 = bf16, 2 = f16
+  static constexpr int kEmbDtype = std::is_same<W, bf16>::value ? 1 : is_half16<W>::value ? 2 : 0;
   bool fp8w_ = false;
   W* deq_buf_ = nullptr;  // bf16 image of the largest fp8 weight (prefill operand)
   // pack rows of a raw f32 tensor as fp8 + scales into l (rows [row0, row0 + rows))
@@ -313,7 +334,7 @@ class Model : public ModelBase {
     if (t.numel() != (int64_t)rows * cols || cols != l.k)
       throw std::runtime_error("shape mismatch for " + name + " (fp8 pack)");
     launch_quant_fp8_rows(t.p, cols, rows, cols, l.w8 + (size_t)row0 * l.stride(), l.stride() * rstride, l.ws + row0, 0,
-                          rstride);
+                          rstride, weight_counts());
   }
   Lin<W> alloc_fp8(int n, int k) {
     if (k % 16) throw std::runtime_error("fp8 weights need K % 16 == 0");
@@ -577,8 +598,16 @@ E* Model<T, TS>::pack_rows(E* dst, int dst_row0, const std::string& name, int ro
   if (t.numel() != (int64_t)rows * cols)
     throw std::runtime_error("shape mismatch for " + name + ": expected " + std::to_string(rows) + "x" +
                              std::to_string(cols) + ", got " + std::to_string(t.numel()) + " elements");
-  launch_convert<E>(t.p, cols, dst + (int64_t)dst_row0 * kpad, kpad, rows, cols, 0);
+  launch_convert<E>(t.p, cols, dst + (int64_t)dst_row0 * kpad, kpad, rows, cols, 0, weight_counts());
+  if constexpr (std::is_same<T, f16>::value) check_f16_range(name);
   return dst;
+}
+// ANYREF_MODE_PERF_F16: a weight past f16's range (|w| > 65504) would be stored as inf and turn the outputs into NaN
+template <typename T, typename TS>
+void Model<T, TS>::check_f16_range(const std::string& name) {
+  unsigned long long n = 0;
+  HIP_TRY(hipMemcpy(&n, weight_counts() + 1, sizeof(n), hipMemcpyDeviceToHost));
+  if (n) throw std::runtime_error(name + ": " + std::to_string(n) + " weight(s) outside the f16 range (|w| > 65504)");
 }
 template <typename T, typename TS>
 template <typename E>
@@ -875,7 +904,8 @@ void Model<T, TS>::finalize() {
       neck2_.n = C;
       neck2_.k = 9 * C;
       neck2_.w = talloc<WS>(r.size());
-      launch_convert<WS>(rf, 9 * C, neck2_.w, 9 * C, C, 9 * C, 0);
+      launch_convert<WS>(rf, 9 * C, neck2_.w, 9 * C, C, 9 * C, 0, weight_counts());
+      if constexpr (std::is_same<T, f16>::value) check_f16_range(p + "neck.2.weight");
       HIP_TRY(hipStreamSynchronize(0));
       dfree(rf);
     }
@@ -1087,6 +1117,7 @@ void Model<T, TS>::finalize() {
   HIP_TRY(hipEventCreateWithFlags(&ev_fork_, ev_flags));
   HIP_TRY(hipEventCreateWithFlags(&ev_sam_, ev_flags));
   HIP_TRY(hipDeviceSynchronize());
+  close_weight_counts();
   drop_raw();
   finalized_ = true;
 }
@@ -1304,8 +1335,8 @@ void Model<T, TS>::llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev
       a.A = l_h_; a.lda = H; a.W = L.qkv.w; a.ldw = L.qkv.stride(); a.M = R; a.N = 3 * H; a.K = H;
       a.slabs_out = qkv_slabs_; a.slabs = 2;
       launch_gemm<T>(a, s);
-      launch_rope_cache_slabs(qkv_slabs_, qkv_slabs_ + (size_t)R * 3 * H, B, Sp, nh, hd, nullptr, lens_dev, rope_tab_, l_q_, kc,
-                              vc, S, qkeep, s, QF32);
+      launch_rope_cache_slabs<Q>(qkv_slabs_, qkv_slabs_ + (size_t)R * 3 * H, B, Sp, nh, hd, nullptr, lens_dev, rope_tab_, l_q_,
+                                 kc, vc, S, qkeep, s);
     } else {
       gemm(s, l_h_, H, L.qkv, l_qkv_, 3 * H, R, ACT_NONE, QF32);
       launch_rope_cache<Q>(l_qkv_, B, Sp, nh, hd, nullptr, lens_dev, rope_tab_, l_q_, kc, vc, S, qkeep, s);
@@ -1389,7 +1420,7 @@ void Model<T, TS>::llm_decode_step(hipStream_t s, int B, bool keep_q) {
   h.xn_out = hidden_all_; h.xn_row_map = rowmap_dev_; h.xn_ld = H;
   launch_gemv<T>(h, s);
   // argmax, pos += 1, and the next step's embedding row / cache row index / key count
-  launch_argmax_next(l_logits_, B, c.llm_vocab, c.llm_vocab, next_dev_, pos_dev_, emb_table_, sizeof(W) == 2, H, S, d_x_,
+  launch_argmax_next(l_logits_, B, c.llm_vocab, c.llm_vocab, next_dev_, pos_dev_, emb_table_, kEmbDtype, H, S, d_x_,
                      rowmap_dev_, kvlen_dev_, s);
 }
 
@@ -1689,7 +1720,7 @@ int Model<T, TS>::splice_inputs(hipStream_t s, const int64_t* input_ids, const i
   if (Sp > c.llm_max_seq) throw std::runtime_error("prompt longer than llm_max_seq");
   HIP_TRY(hipMemcpyAsync(ids_dev_, input_ids, (size_t)B * Lmax * 8, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(lens_dev_, lens, B * 4, hipMemcpyHostToDevice, s));
-  launch_embed_splice(ids_dev_, lens_dev_, B, Lmax, emb_table_, sizeof(W) == 2, c.llm_vocab, img_feat_, n_img, l_x_, Sp,
+  launch_embed_splice(ids_dev_, lens_dev_, B, Lmax, emb_table_, kEmbDtype, c.llm_vocab, img_feat_, n_img, l_x_, Sp,
                       H, slen_dev_, s);
   if (n_extra > 0) {
     if (n_extra > (int)cfg.max_batch * std::max(cfg.max_seg, 64)) throw std::runtime_error("too many extra slots");
@@ -1962,7 +1993,7 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
     h.x = l_xlast_; h.ldx = H; gemv_w(h, lm_head_); h.y = l_logits_; h.ldy = c.llm_vocab; h.B = B; h.N = c.llm_vocab;
     h.K = H;
     launch_gemv<T>(h, s);
-    launch_argmax_next(l_logits_, B, c.llm_vocab, c.llm_vocab, next_dev_, pos_dev_, emb_table_, sizeof(W) == 2, H, S, d_x_,
+    launch_argmax_next(l_logits_, B, c.llm_vocab, c.llm_vocab, next_dev_, pos_dev_, emb_table_, kEmbDtype, H, S, d_x_,
                        rowmap_dev_, kvlen_dev_, s);
   }
   // greedy loop (HF greedy search: stop a row at EOS, pad finished rows; anyref.py:704-716)
@@ -2140,6 +2171,7 @@ std::unique_ptr<ModelBase> make_model(const anyref_config& cfg, int device) {
     if (sam_bf16) return std::unique_ptr<ModelBase>(new Model<bf16, bf16>(cfg, device));
     return std::unique_ptr<ModelBase>(new Model<bf16, f16>(cfg, device));
   }
+  if (cfg.mode == ANYREF_MODE_PERF_F16) return std::unique_ptr<ModelBase>(new Model<f16, f16>(cfg, device));
   throw std::runtime_error("unknown mode");
 }
 

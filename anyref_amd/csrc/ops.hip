@@ -478,29 +478,47 @@ template void launch_im2col_3x3<sp16>(const void*, int, int, int, void*, hipStre
 // ---------------------------------------------------------------------------------------------
 // converts / adds
 // ---------------------------------------------------------------------------------------------
+// counts (optional, 16-bit T): counts[0] += elements with float(T(x)) != x, counts[1] += finite x that became inf
 template <typename T>
 __global__ void convert_kernel(const float* __restrict__ in, int64_t ld_in, T* __restrict__ out,
-                               int64_t ld_out, int rows, int cols) {
+                               int64_t ld_out, int rows, int cols, unsigned long long* __restrict__ counts) {
   const int64_t total = (int64_t)rows * cols;
+  unsigned inexact = 0, overflow = 0;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / cols, c = i % cols;
-    st1<T>(out + r * ld_out, (int)c, in[r * ld_in + c]);
+    const float x = in[r * ld_in + c];
+    st1<T>(out + r * ld_out, (int)c, x);
+    if constexpr (std::is_same<T, bf16>::value || is_half16<T>::value) {
+      if (!counts) continue;
+      const float y = to_f32<T>(from_f32<T>(x));
+      // NaN stays NaN: held as handed over (x != x would count every NaN)
+      inexact += (y != x && !(__builtin_isnan(x) && __builtin_isnan(y))) ? 1u : 0u;
+      overflow += (__builtin_isfinite(x) && !__builtin_isfinite(y)) ? 1u : 0u;
+    }
+  }
+  if constexpr (std::is_same<T, bf16>::value || is_half16<T>::value) {
+    if (!counts) return;
+    const float fi = wave_sum((float)inexact), fo = wave_sum((float)overflow);  // <= 64 * (elements per lane): exact in f32
+    if ((threadIdx.x & 63) == 0) {
+      if (fi > 0.f) atomicAdd(&counts[0], (unsigned long long)fi);
+      if (fo > 0.f) atomicAdd(&counts[1], (unsigned long long)fo);
+    }
   }
 }
 template <typename T>
 void launch_convert(const float* in, int64_t ld_in, void* out, int64_t ld_out, int rows, int cols,
-                    hipStream_t s) {
+                    hipStream_t s, unsigned long long* counts) {
   const int64_t total = (int64_t)rows * cols;
   if (total <= 0) return;
   const int grid = (int)(cdiv64(total, 256) < 8192 ? cdiv64(total, 256) : 8192);
   hipLaunchKernelGGL((convert_kernel<T>), dim3(grid), dim3(256), 0, s, in, ld_in, reinterpret_cast<T*>(out),
-                     ld_out, rows, cols);
+                     ld_out, rows, cols, counts);
 }
-template void launch_convert<float>(const float*, int64_t, void*, int64_t, int, int, hipStream_t);
-template void launch_convert<bf16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t);
-template void launch_convert<f16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t);
-template void launch_convert<sp16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t);
+template void launch_convert<float>(const float*, int64_t, void*, int64_t, int, int, hipStream_t, unsigned long long*);
+template void launch_convert<bf16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t, unsigned long long*);
+template void launch_convert<f16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t, unsigned long long*);
+template void launch_convert<sp16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t, unsigned long long*);
 
 // split-pair rows back to f32 (tests, and wherever an f32 view of an sp16 matrix is needed): out[r, c] = hi + lo
 __global__ void unsplit_kernel(const sp16* __restrict__ in, int64_t ld_in, float* __restrict__ out, int64_t ld_out,
@@ -546,6 +564,7 @@ void launch_add_rows_to(const float* a, const float* b, int bmod, void* out, int
 }
 template void launch_add_rows_to<float>(const float*, const float*, int, void*, int, int, hipStream_t);
 template void launch_add_rows_to<bf16>(const float*, const float*, int, void*, int, int, hipStream_t);
+template void launch_add_rows_to<f16>(const float*, const float*, int, void*, int, int, hipStream_t);
 
 __global__ void add_vec_kernel(const float* __restrict__ a, const float* __restrict__ v, float* __restrict__ out,
                                int M, int D) {
@@ -612,6 +631,7 @@ void launch_im2col_conv1(const float* img, int n, int Hh, int Ww, int k, int st,
 }
 template void launch_im2col_conv1<float>(const float*, int, int, int, int, int, void*, hipStream_t);
 template void launch_im2col_conv1<bf16>(const float*, int, int, int, int, int, void*, hipStream_t);
+template void launch_im2col_conv1<f16>(const float*, int, int, int, int, int, void*, hipStream_t);
 template void launch_im2col_conv1<sp16>(const float*, int, int, int, int, int, void*, hipStream_t);
 
 // f-4: ImageBind audio head tail (imagebind_model.py:425-428): y = x / max(||x||_2, 1e-12) * scale, one block per row
@@ -634,8 +654,22 @@ void launch_l2norm_scale(const float* x, int rows, int D, float scale, float* y,
 // ---------------------------------------------------------------------------------------------
 // token embedding gather + image splice.  One block per output row.
 // ---------------------------------------------------------------------------------------------
+// row `id` of an embedding table [vocab, D] to f32; dtype 0 = f32, 1 = bf16, 2 = f16 (the table is packed as the mode's
+// weight type)
+__device__ inline void table_row_to_f32(const void* table, int dtype, int64_t id, int D, float* dst, int t0, int nt) {
+  if (dtype == 1) {
+    const bf16* src = reinterpret_cast<const bf16*>(table) + id * D;
+    for (int d = t0; d < D; d += nt) dst[d] = bf2f(src[d]);
+  } else if (dtype == 2) {
+    const f16* src = reinterpret_cast<const f16*>(table) + id * D;
+    for (int d = t0; d < D; d += nt) dst[d] = h2f(src[d]);
+  } else {
+    const float* src = reinterpret_cast<const float*>(table) + id * D;
+    for (int d = t0; d < D; d += nt) dst[d] = src[d];
+  }
+}
 __global__ void embed_splice_kernel(const int64_t* __restrict__ ids, const int* __restrict__ lens, int B,
-                                    int Lmax, const void* __restrict__ table, int is_bf16, int vocab,
+                                    int Lmax, const void* __restrict__ table, int emb_dtype, int vocab,
                                     const float* __restrict__ img_feat, int n_img, float* __restrict__ x,
                                     int Smax, int D, int* __restrict__ out_len) {
   const int b = blockIdx.y, srow = blockIdx.x;
@@ -669,20 +703,14 @@ __global__ void embed_splice_kernel(const int64_t* __restrict__ ids, const int* 
     for (int d = threadIdx.x; d < D; d += blockDim.x) dst[d] = 0.f;
     return;
   }
-  if (is_bf16) {
-    const bf16* src = reinterpret_cast<const bf16*>(table) + id * D;
-    for (int d = threadIdx.x; d < D; d += blockDim.x) dst[d] = bf2f(src[d]);
-  } else {
-    const float* src = reinterpret_cast<const float*>(table) + id * D;
-    for (int d = threadIdx.x; d < D; d += blockDim.x) dst[d] = src[d];
-  }
+  table_row_to_f32(table, emb_dtype, id, D, dst, threadIdx.x, blockDim.x);
 }
 void launch_embed_splice(const int64_t* ids, const int* lens, int B, int Lmax, const void* emb_table,
-                         int emb_is_bf16, int vocab, const float* img_feat, int n_img, float* x, int Smax, int D,
+                         int emb_dtype, int vocab, const float* img_feat, int n_img, float* x, int Smax, int D,
                          int* out_len, hipStream_t s) {
   dim3 grid(Lmax + n_img, B);
   if ((int)grid.x > Smax) grid.x = Smax;
-  hipLaunchKernelGGL(embed_splice_kernel, grid, dim3(256), 0, s, ids, lens, B, Lmax, emb_table, emb_is_bf16,
+  hipLaunchKernelGGL(embed_splice_kernel, grid, dim3(256), 0, s, ids, lens, B, Lmax, emb_table, emb_dtype,
                      vocab, img_feat, n_img, x, Smax, D, out_len);
 }
 
@@ -747,33 +775,33 @@ __global__ void rope_cache_kernel(const TIN* __restrict__ qkv, int B, int S, int
     vc[co + d + half] = from_f32<T>(v2);
   }
 }
-// bf16 rows, 16-byte accesses: a lane takes 8 consecutive d of the first half and the 8 partners of the second half
-// (six 16-byte loads, six stores) -- the same f32 operations as the scalar kernel above, bit-identical results.
-template <bool SLABS>
-__global__ __launch_bounds__(256) void rope_cache_vec_kernel(const bf16* __restrict__ qkv, const float* __restrict__ slab0,
+// 16-bit rows (E = bf16 / f16), 16-byte accesses: a lane takes 8 consecutive d of the first half and the 8 partners of the
+// second half (six 16-byte loads, six stores) -- the same f32 operations as the scalar kernel above, bit-identical results.
+template <typename E, bool SLABS>
+__global__ __launch_bounds__(256) void rope_cache_vec_kernel(const E* __restrict__ qkv, const float* __restrict__ slab0,
                                                              const float* __restrict__ slab1, int S, int H, int hd,
                                                              const int* __restrict__ pos0, const int* __restrict__ lens,
-                                                             const float* __restrict__ cs_tab, bf16* __restrict__ q_out,
-                                                             bf16* __restrict__ kc, bf16* __restrict__ vc, int maxS,
-                                                             bf16* __restrict__ q_keep) {
+                                                             const float* __restrict__ cs_tab, E* __restrict__ q_out,
+                                                             E* __restrict__ kc, E* __restrict__ vc, int maxS,
+                                                             E* __restrict__ q_keep) {
   const int srow = blockIdx.x, b = blockIdx.y;
   if (lens && srow >= lens[b]) return;
   const int pos = (pos0 ? pos0[b] : 0) + srow;
   const int half = hd / 2, per = half / 8;  // lanes per head
   const int64_t roff = ((int64_t)b * S + srow) * 3 * H * hd;
-  const bf16* base = qkv + roff;
-  // 8 values at column c of this row: the GEMM's bf16 output, or the sum of its two f32 K slices rounded the same way
+  const E* base = qkv + roff;
+  // 8 values at column c of this row: the GEMM's E output, or the sum of its two f32 K slices rounded the same way
   auto ld8 = [&](int c, float (&o)[8]) {
     if constexpr (SLABS) {
       const float4v a0 = *reinterpret_cast<const float4v*>(slab0 + roff + c), a1 = *reinterpret_cast<const float4v*>(slab0 + roff + c + 4);
       const float4v b0 = *reinterpret_cast<const float4v*>(slab1 + roff + c), b1 = *reinterpret_cast<const float4v*>(slab1 + roff + c + 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        o[e] = bf2f(f2bf(a0[e] + b0[e]));
-        o[4 + e] = bf2f(f2bf(a1[e] + b1[e]));
+        o[e] = to_f32<E>(from_f32<E>(a0[e] + b0[e]));
+        o[4 + e] = to_f32<E>(from_f32<E>(a1[e] + b1[e]));
       }
     } else {
-      Vec16<bf16>::unpack(*reinterpret_cast<const uint4v*>(base + c), o);
+      Vec16<E>::unpack(*reinterpret_cast<const uint4v*>(base + c), o);
     }
   };
   for (int i = threadIdx.x; i < H * per; i += blockDim.x) {
@@ -790,20 +818,20 @@ __global__ __launch_bounds__(256) void rope_cache_vec_kernel(const bf16* __restr
     ld8((H + h) * hd + d + half, k2);
     ld8((2 * H + h) * hd + d, va);
     ld8((2 * H + h) * hd + d + half, vb);
-    bf16 qa[8], qb[8], ka[8], kb[8], v1[8], v2[8];
+    E qa[8], qb[8], ka[8], kb[8], v1[8], v2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      v1[e] = from_f32<bf16>(va[e]);   // exact: va / vb are bf16 values
-      v2[e] = from_f32<bf16>(vb[e]);
+      v1[e] = from_f32<E>(va[e]);   // exact: va / vb are E values
+      v2[e] = from_f32<E>(vb[e]);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      qa[e] = from_f32<bf16>(q1[e] * cs[e] - q2[e] * sn[e]);
-      qb[e] = from_f32<bf16>(q2[e] * cs[e] + q1[e] * sn[e]);
-      ka[e] = from_f32<bf16>(k1[e] * cs[e] - k2[e] * sn[e]);
-      kb[e] = from_f32<bf16>(k2[e] * cs[e] + k1[e] * sn[e]);
+      qa[e] = from_f32<E>(q1[e] * cs[e] - q2[e] * sn[e]);
+      qb[e] = from_f32<E>(q2[e] * cs[e] + q1[e] * sn[e]);
+      ka[e] = from_f32<E>(k1[e] * cs[e] - k2[e] * sn[e]);
+      kb[e] = from_f32<E>(k2[e] * cs[e] + k1[e] * sn[e]);
     }
-    bf16* qo = q_out + (((int64_t)b * S + srow) * H + h) * hd;
+    E* qo = q_out + (((int64_t)b * S + srow) * H + h) * hd;
     *reinterpret_cast<uint4v*>(qo + d) = *reinterpret_cast<const uint4v*>(qa);
     *reinterpret_cast<uint4v*>(qo + d + half) = *reinterpret_cast<const uint4v*>(qb);
     const int64_t co = (((int64_t)b * maxS + pos) * H + h) * hd;
@@ -825,10 +853,10 @@ void launch_rope_cache(const void* qkv, int B, int S, int H, int hd, const int* 
     const bool al = !(((uintptr_t)qkv | (uintptr_t)q_out | (uintptr_t)kc | (uintptr_t)vc | (uintptr_t)q_keep |
                        (uintptr_t)cs_tab) & 15);
     if (hd % 16 == 0 && al) {
-      hipLaunchKernelGGL(rope_cache_vec_kernel<false>, dim3(S, B), dim3(256), 0, s, reinterpret_cast<const bf16*>(qkv),
+      hipLaunchKernelGGL((rope_cache_vec_kernel<T, false>), dim3(S, B), dim3(256), 0, s, reinterpret_cast<const T*>(qkv),
                          (const float*)nullptr, (const float*)nullptr, S, H, hd,
-                         pos0, lens, cs_tab, reinterpret_cast<bf16*>(q_out), reinterpret_cast<bf16*>(kc),
-                         reinterpret_cast<bf16*>(vc), maxS, reinterpret_cast<bf16*>(q_keep));
+                         pos0, lens, cs_tab, reinterpret_cast<T*>(q_out), reinterpret_cast<T*>(kc),
+                         reinterpret_cast<T*>(vc), maxS, reinterpret_cast<T*>(q_keep));
       return;
     }
   }
@@ -878,26 +906,35 @@ __global__ __launch_bounds__(256) void rope_cache_slabs_f32_kernel(const float* 
     *reinterpret_cast<float4v*>(vc + co + d + half) = v2;
   }
 }
+template <typename T>
 void launch_rope_cache_slabs(const float* slab0, const float* slab1, int B, int S, int H, int hd, const int* pos0,
                              const int* lens, const float* cs_tab, void* q_out, void* kc, void* vc, int maxS, void* q_keep,
-                             hipStream_t s, bool out_f32) {
+                             hipStream_t s) {
   if (hd % 16 || (((uintptr_t)slab0 | (uintptr_t)slab1 | (uintptr_t)q_out | (uintptr_t)kc | (uintptr_t)vc | (uintptr_t)q_keep |
                    (uintptr_t)cs_tab) & 15))
     throw std::runtime_error("rope_cache_slabs: head dim % 16 and 16-byte aligned buffers");
-  if (out_f32) {
+  if constexpr (std::is_same<T, float>::value) {
     hipLaunchKernelGGL(rope_cache_slabs_f32_kernel, dim3(S, B), dim3(256), 0, s, slab0, slab1, S, H, hd, pos0, lens, cs_tab,
                        reinterpret_cast<float*>(q_out), reinterpret_cast<float*>(kc), reinterpret_cast<float*>(vc), maxS,
                        reinterpret_cast<float*>(q_keep));
-    return;
+  } else {
+    hipLaunchKernelGGL((rope_cache_vec_kernel<T, true>), dim3(S, B), dim3(256), 0, s, (const T*)nullptr, slab0, slab1, S, H,
+                       hd, pos0, lens, cs_tab, reinterpret_cast<T*>(q_out), reinterpret_cast<T*>(kc),
+                       reinterpret_cast<T*>(vc), maxS, reinterpret_cast<T*>(q_keep));
   }
-  hipLaunchKernelGGL(rope_cache_vec_kernel<true>, dim3(S, B), dim3(256), 0, s, (const bf16*)nullptr, slab0, slab1, S, H, hd,
-                     pos0, lens, cs_tab, reinterpret_cast<bf16*>(q_out), reinterpret_cast<bf16*>(kc),
-                     reinterpret_cast<bf16*>(vc), maxS, reinterpret_cast<bf16*>(q_keep));
 }
+template void launch_rope_cache_slabs<float>(const float*, const float*, int, int, int, int, const int*, const int*,
+                                             const float*, void*, void*, void*, int, void*, hipStream_t);
+template void launch_rope_cache_slabs<bf16>(const float*, const float*, int, int, int, int, const int*, const int*,
+                                            const float*, void*, void*, void*, int, void*, hipStream_t);
+template void launch_rope_cache_slabs<f16>(const float*, const float*, int, int, int, int, const int*, const int*,
+                                           const float*, void*, void*, void*, int, void*, hipStream_t);
 template void launch_rope_cache<float>(const void*, int, int, int, int, const int*, const int*, const float*,
                                        void*, void*, void*, int, void*, hipStream_t);
 template void launch_rope_cache<bf16>(const void*, int, int, int, int, const int*, const int*, const float*,
                                       void*, void*, void*, int, void*, hipStream_t);
+template void launch_rope_cache<f16>(const void*, int, int, int, int, const int*, const int*, const float*,
+                                     void*, void*, void*, int, void*, hipStream_t);
 template <typename T>
 void launch_rope_cache_f32(const float* qkv, int B, int H, int hd, const int* pos, const float* cs_tab,
                            void* q_out, void* kc, void* vc, int maxS, void* q_keep, hipStream_t s) {
@@ -919,22 +956,17 @@ template void launch_rope_cache_f32<float>(const float*, int, int, int, const in
                                            void*, int, void*, hipStream_t);
 template void launch_rope_cache_f32<bf16>(const float*, int, int, int, const int*, const float*, void*, void*,
                                           void*, int, void*, hipStream_t);
+template void launch_rope_cache_f32<f16>(const float*, int, int, int, const int*, const float*, void*, void*,
+                                         void*, int, void*, hipStream_t);
 
-__global__ void embed_rows_kernel(const int64_t* __restrict__ ids, const void* __restrict__ table, int is_bf16,
+__global__ void embed_rows_kernel(const int64_t* __restrict__ ids, const void* __restrict__ table, int dtype,
                                   int D, float* __restrict__ x) {
   const int b = blockIdx.x;
-  const int64_t id = ids[b];
-  if (is_bf16) {
-    const bf16* src = reinterpret_cast<const bf16*>(table) + id * D;
-    for (int d = threadIdx.x; d < D; d += blockDim.x) x[(int64_t)b * D + d] = bf2f(src[d]);
-  } else {
-    const float* src = reinterpret_cast<const float*>(table) + id * D;
-    for (int d = threadIdx.x; d < D; d += blockDim.x) x[(int64_t)b * D + d] = src[d];
-  }
+  table_row_to_f32(table, dtype, ids[b], D, x + (int64_t)b * D, threadIdx.x, blockDim.x);
 }
-void launch_embed_rows(const int64_t* ids, int B, const void* table, int is_bf16, int D, float* x,
+void launch_embed_rows(const int64_t* ids, int B, const void* table, int dtype, int D, float* x,
                        hipStream_t s) {
-  hipLaunchKernelGGL(embed_rows_kernel, dim3(B), dim3(256), 0, s, ids, table, is_bf16, D, x);
+  hipLaunchKernelGGL(embed_rows_kernel, dim3(B), dim3(256), 0, s, ids, table, dtype, D, x);
 }
 __global__ void decode_index_kernel(const int* __restrict__ pos, int B, int maxS, int* __restrict__ row_map,
                                     int* __restrict__ kvlen) {
@@ -981,6 +1013,7 @@ void launch_swiglu(const void* gu, int M, int F, void* out, hipStream_t s) {
 }
 template void launch_swiglu<float>(const void*, int, int, void*, hipStream_t);
 template void launch_swiglu<bf16>(const void*, int, int, void*, hipStream_t);
+template void launch_swiglu<f16>(const void*, int, int, void*, hipStream_t);
 
 // argmax, first index on ties (torch.argmax on CPU returns the first maximal index).  One 1024-thread
 // workgroup per row, 16-byte loads all issued before the first compare (the row is read once, the
@@ -1007,8 +1040,8 @@ __device__ __forceinline__ void argmax_take(float v, int i, float& best, int& bi
 // the chosen token -> nx.x[b], KV-cache row index and key count of the (bumped) position -- instead of two more
 // one-workgroup launches at the head of every step.
 struct ArgmaxNext {
-  const void* table = nullptr;  // [vocab, D] bf16 or f32
-  int is_bf16 = 0, D = 0, maxS = 0;
+  const void* table = nullptr;  // [vocab, D] f32 / bf16 / f16 (dtype 0 / 1 / 2)
+  int dtype = 0, D = 0, maxS = 0;
   float* x = nullptr;           // [B, D]
   int* row_map = nullptr;       // [B] b * maxS + pos
   int* kvlen = nullptr;         // [B] pos + 1
@@ -1073,23 +1106,17 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
   __syncthreads();
   const int64_t id = si[0];
   float* dst = nx.x + (int64_t)blockIdx.x * nx.D;
-  if (nx.is_bf16) {
-    const bf16* src = reinterpret_cast<const bf16*>(nx.table) + id * nx.D;
-    for (int d = tid; d < nx.D; d += NT) dst[d] = bf2f(src[d]);
-  } else {
-    const float* src = reinterpret_cast<const float*>(nx.table) + id * nx.D;
-    for (int d = tid; d < nx.D; d += NT) dst[d] = src[d];
-  }
+  table_row_to_f32(nx.table, nx.dtype, id, nx.D, dst, tid, NT);
 }
 void launch_argmax(const float* x, int M, int N, int ldx, int64_t* out, hipStream_t s, int* bump) {
   if (M <= 0) return;
   hipLaunchKernelGGL(argmax_kernel, dim3(M), dim3(1024), 0, s, x, N, ldx, out, bump, ArgmaxNext{});
 }
-void launch_argmax_next(const float* x, int M, int N, int ldx, int64_t* out, int* pos, const void* table, int is_bf16,
+void launch_argmax_next(const float* x, int M, int N, int ldx, int64_t* out, int* pos, const void* table, int dtype,
                         int D, int maxS, float* x_next, int* row_map, int* kvlen, hipStream_t s) {
   if (M <= 0) return;
   ArgmaxNext nx;
-  nx.table = table; nx.is_bf16 = is_bf16; nx.D = D; nx.maxS = maxS; nx.x = x_next; nx.row_map = row_map; nx.kvlen = kvlen;
+  nx.table = table; nx.dtype = dtype; nx.D = D; nx.maxS = maxS; nx.x = x_next; nx.row_map = row_map; nx.kvlen = kvlen;
   hipLaunchKernelGGL(argmax_kernel, dim3(M), dim3(1024), 0, s, x, N, ldx, out, pos, nx);
 }
 
@@ -1586,7 +1613,8 @@ template void launch_fill_rows_bias<f16>(void*, int, const int*, int, const floa
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const float* __restrict__ src, int lds, int K,
                                                              uint8_t* __restrict__ q, int ldq,
-                                                             float* __restrict__ scale, int sstride) {
+                                                             float* __restrict__ scale, int sstride,
+                                                             unsigned long long* __restrict__ inexact) {
   const int n = blockIdx.x, tid = threadIdx.x;
   const float* row = src + (int64_t)n * lds;
   float amax = 0.f;
@@ -1599,17 +1627,27 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const float* __rest
   const float sc = amax > 0.f ? amax / FP8_E4M3_MAX : 1.f;
   if (tid == 0) scale[(int64_t)n * sstride] = sc;
   uint8_t* out = q + (int64_t)n * ldq;
+  unsigned changed = 0;  // elements whose held value q * scale differs from the source
   for (int k = tid * 2; k < K; k += 512) {  // two values per v_cvt_pk_fp8_f32 (RNE, saturating)
     const float a = row[k] / sc, b = k + 1 < K ? row[k + 1] / sc : 0.f;
     const int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
     out[k] = (uint8_t)(w & 255);
     if (k + 1 < K) out[k + 1] = (uint8_t)((w >> 8) & 255);
+    if (inexact) {
+      const auto d = __builtin_amdgcn_cvt_pk_f32_fp8(w, false);
+      changed += (d[0] * sc != row[k]) ? 1u : 0u;
+      if (k + 1 < K) changed += (d[1] * sc != row[k + 1]) ? 1u : 0u;
+    }
+  }
+  if (inexact) {
+    const float c = wave_sum((float)changed);  // <= 64 * K / 256: exact in f32
+    if ((tid & 63) == 0 && c > 0.f) atomicAdd(inexact, (unsigned long long)c);
   }
 }
 void launch_quant_fp8_rows(const float* src, int lds, int N, int K, uint8_t* q, int ldq, float* scale, hipStream_t s,
-                           int scale_stride) {
+                           int scale_stride, unsigned long long* inexact) {
   if (N <= 0) return;
-  hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3(N), dim3(256), 0, s, src, lds, K, q, ldq, scale, scale_stride);
+  hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3(N), dim3(256), 0, s, src, lds, K, q, ldq, scale, scale_stride, inexact);
 }
 
 __global__ __launch_bounds__(256) void dequant_fp8_rows_kernel(const uint8_t* __restrict__ q, int ldq,

@@ -81,7 +81,9 @@ int anyref_op_gemv(int t, void* stream, const float* x, const float* gain, float
     a.ldy = N; a.B = B; a.N = N; a.K = K; a.act = act;
     if (const char* e = getenv("ANYREF_OPTEST_LDW_PAD")) a.ldw = K + atoi(e);  // probe: padded weight rows
     if (t == 3) launch_gemv<sp16>(a, (hipStream_t)stream);  // W bf16, x f32 staged as f32
-    else if (t == 0) launch_gemv<float>(a, (hipStream_t)stream); else launch_gemv<bf16>(a, (hipStream_t)stream);
+    else if (t == 0) launch_gemv<float>(a, (hipStream_t)stream);
+    else if (t == 2) launch_gemv<f16>(a, (hipStream_t)stream);
+    else launch_gemv<bf16>(a, (hipStream_t)stream);
   });
 }
 
@@ -95,7 +97,8 @@ int anyref_op_gemv_xn(int t, void* stream, const float* x, const float* gain, fl
     a.xn_out = xn_out; a.xn_row_map = xn_row_map; a.xn_ld = xn_ld;
     if (t == 0) launch_gemv<float>(a, (hipStream_t)stream);
     else if (t == 1) launch_gemv<bf16>(a, (hipStream_t)stream);
-    else throw std::runtime_error("op_gemv_xn: t = 0 / 1");
+    else if (t == 2) launch_gemv<f16>(a, (hipStream_t)stream);
+    else throw std::runtime_error("op_gemv_xn: t = 0 / 1 / 2");
   });
 }
 
@@ -105,7 +108,7 @@ int anyref_op_decode_attn(int t, void* stream, const float* qkv, int B, int H, i
                           const float* cs_tab, void* kc, void* vc, int maxS, float scale, float* out, void* q_keep,
                           int force_fallback) {
   OP_GUARD({
-    if (t != 0 && t != 1) throw std::runtime_error("op_decode_attn: t = 0 / 1");
+    if (t != 0 && t != 1 && t != 2) throw std::runtime_error("op_decode_attn: t = 0 / 1 / 2");
     hipStream_t st = (hipStream_t)stream;
     // kv_len[b] = pos[b] + 1 (the model's kvlen_dev_, written by the argmax of the step before)
     std::vector<int> h(B);
@@ -117,6 +120,9 @@ int anyref_op_decode_attn(int t, void* stream, const float* qkv, int B, int H, i
     if (t == 0)
       launch_decode_step_attn<float>(qkv, B, H, hd, pos, (const int*)kv_len.p, cs_tab, q_tmp.p, kc, vc, maxS, scale, out,
                                      q_keep, st, force_fallback != 0);
+    else if (t == 2)
+      launch_decode_step_attn<f16>(qkv, B, H, hd, pos, (const int*)kv_len.p, cs_tab, q_tmp.p, kc, vc, maxS, scale, out,
+                                   q_keep, st, force_fallback != 0);
     else
       launch_decode_step_attn<bf16>(qkv, B, H, hd, pos, (const int*)kv_len.p, cs_tab, q_tmp.p, kc, vc, maxS, scale, out,
                                     q_keep, st, force_fallback != 0);
@@ -128,11 +134,15 @@ int anyref_op_rope_cache(int t, void* stream, const void* qkv, const float* slab
                          void* vc, int maxS, void* q_keep) {
   OP_GUARD({
     hipStream_t st = (hipStream_t)stream;
-    if (t != 0 && t != 1) throw std::runtime_error("op_rope_cache: t = 0 / 1");
-    if (slab0)
-      launch_rope_cache_slabs(slab0, slab1, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st, t == 0);
-    else if (t == 0)
+    if (t != 0 && t != 1 && t != 2) throw std::runtime_error("op_rope_cache: t = 0 / 1 / 2");
+    if (slab0) {
+      if (t == 0) launch_rope_cache_slabs<float>(slab0, slab1, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st);
+      else if (t == 2) launch_rope_cache_slabs<f16>(slab0, slab1, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st);
+      else launch_rope_cache_slabs<bf16>(slab0, slab1, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st);
+    } else if (t == 0)
       launch_rope_cache<float>(qkv, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st);
+    else if (t == 2)
+      launch_rope_cache<f16>(qkv, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st);
     else
       launch_rope_cache<bf16>(qkv, B, S, H, hd, pos0, lens, cs_tab, q_out, kc, vc, maxS, q_keep, st);
   });
@@ -141,6 +151,7 @@ int anyref_op_rope_cache(int t, void* stream, const void* qkv, const float* slab
 int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_t* out, int32_t* pos, const void* table,
                      int is_bf16, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen) {
   OP_GUARD({
+    if (table && (is_bf16 < 0 || is_bf16 > 2)) throw std::runtime_error("op_argmax: table dtype 0 / 1 / 2");
     if (table)
       launch_argmax_next(x, M, N, ldx, out, pos, table, is_bf16, D, maxS, x_next, row_map, kvlen, (hipStream_t)stream);
     else

@@ -67,7 +67,7 @@ def _c_config(cfg: AnyRefConfig, mode: int, max_batch: int, max_seg: int) -> _li
 
 _NEEDS_HANDLE = frozenset({
     "generate", "model_forward_new", "forward", "__call__", "encode_images", "sam_encode", "mask_decode", "llm_forward",
-    "seg_tail", "postprocess", "audio_encode", "device_bytes", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
+    "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
     "stamps_enable", "stamps_read", "set_side_share"})
 
 
@@ -91,7 +91,7 @@ class AnyRefForCausalLM:
         self.imagebind_ckpt = kwargs.pop("imagebind_ckpt", "model/ImageBind/imagebind_huge.pth")
         self.cfg = cfg
         self.mode = {"parity": _lib.MODE_PARITY, "perf": _lib.MODE_PERF, "perf_fp8w": _lib.MODE_PERF_FP8W,
-                     "parity16": _lib.MODE_PARITY16}[mode]
+                     "parity16": _lib.MODE_PARITY16, "perf_f16": _lib.MODE_PERF_F16}[mode]
         self.mode_name = mode
         self.device_index = device
         self.device = torch.device("cuda", device)
@@ -205,7 +205,10 @@ class AnyRefForCausalLM:
         (anyref.py:188-209: seg_token_idx, out_dim, vision_pretrained, add_audio_encoder, rephrase_weight, ...).
         The handle is built at `.cuda()` / first use, after the caller's `initialize_*`, `resize_token_embeddings`
         and adapter merge.  `torch_dtype` is accepted for signature parity; the arithmetic type is `mode`
-        ("perf" = bf16 storage, fp32 accumulate; "parity" = fp32), default perf."""
+        ("perf" = bf16 storage, fp32 accumulate; "parity" = fp32), default perf.  The reference evaluates in fp16
+        (`torch_dtype=torch.float16`), so its checkpoints are fp16: `mode="perf_f16"` (f16 storage, fp32 accumulate, same
+        bytes and rate as perf) holds such weights bit for bit, where perf rounds them to bf16 (`inexact_weights` counts
+        the elements that changed)."""
         import json
         import os
         from .checkpoint import read_hf_dir, llm_config_from_hf
@@ -324,6 +327,14 @@ class AnyRefForCausalLM:
     @property
     def device_bytes(self) -> int:
         return int(self.lib.anyref_device_bytes(self.h))
+
+    @property
+    def inexact_weights(self) -> int:
+        """Weight elements the handle holds in a value other than the one it was given (anyref_inexact_weights): 0 in
+        "parity", 0 in "perf_f16" for an fp16 checkpoint, most elements of that checkpoint in "perf" (bf16 storage)."""
+        n = C.c_int64(0)
+        self._check(self.lib.anyref_inexact_weights(self.h, C.byref(n)), "inexact_weights")
+        return int(n.value)
 
     def set_seg_token_idx(self, seg_token_idx):
         """`seg_token_idx` kwarg of the reference constructor (anyref.py:197-200), changeable later."""

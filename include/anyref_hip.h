@@ -46,6 +46,12 @@ extern "C" {
  * in PARITY.  Inputs must be weights that are exactly representable in bf16 (the synthetic workloads round once; a real
  * fp32 SAM checkpoint is rounded to bf16 at finalize, as the reference's own fp16 evaluation rounds it to fp16). */
 #define ANYREF_MODE_PARITY16 3
+/* PERF with f16 in place of bf16: the LLaMA, CLIP, audio and SAM encoder weights and GEMM A-operands, the KV cache and the
+ * attention operands are IEEE half (11 significant bits against bf16's 8, same MFMA / dot2 rate, same bytes); residual streams,
+ * norms, accumulation, the mask decoder and the logits stay f32 as in PERF.  Holds an fp16 checkpoint (the reference's own
+ * evaluation dtype) bit for bit; f16 activations saturate past 65504 as in the reference's fp16 run.  finalize fails, naming
+ * the tensor, if a weight lies outside the f16 range.  fp8 weights are not offered with it. */
+#define ANYREF_MODE_PERF_F16 4
 
 typedef struct anyref_config {
   int32_t abi_version; /* = ANYREF_ABI_VERSION */
@@ -276,8 +282,12 @@ int anyref_stamps_spread(anyref_handle* h, int64_t idx, double* start_spread_us,
 
 /* Bytes of HBM the handle holds (weights + workspaces), for sizing reports. */
 int64_t anyref_device_bytes(anyref_handle* h);
-/* Name of the compute mode's arithmetic ("f32" / "bf16"). */
+/* Name of the compute mode's arithmetic ("f32" / "bf16" / "f16" ...). */
 const char* anyref_mode_name(anyref_handle* h);
+/* After anyref_finalize, in every mode: *out = the number of weight elements the handle holds in a value other than the one
+ * handed to anyref_set_weight (rounded to the mode's 16-bit type, or quantised to fp8 and back in ANYREF_MODE_PERF_FP8W).
+ * 0 in PARITY; 0 in PERF_F16 for an fp16 checkpoint; in PERF that checkpoint loses 3 mantissa bits in most elements. */
+int anyref_inexact_weights(anyref_handle* h, int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,8 @@
  * isolation.  Not part of the drop-in boundary (that is anyref_hip.h).
  * `t` selects the storage type: 0 = f32 (MFMA 16x16x4 f32), 1 = bf16 (MFMA 16x16x32 bf16), 3 = split pairs (ANYREF_MODE_PARITY16: f32
  * operands at the interface, carried as two bf16 terms inside; weights bf16; gemm / gemv / norm / attention entries), 2 = f16 (MFMA 16x16x32
- * f16: the SAM image encoder of the perf build; GEMM, norm and attention entries).
+ * f16: the SAM image encoder of the perf build and every tower of ANYREF_MODE_PERF_F16; GEMM, GEMV, norm, attention, decode
+ * attention and RoPE entries).
  * All pointers are device pointers; `stream` is a hipStream_t.
  */
 #ifndef ANYREF_HIP_OPS_H
@@ -20,28 +21,28 @@ int anyref_op_gemm(int t, void* stream, const void* A, const void* W, const floa
 /* y = act(rmsnorm?(x) W^T) [* (x W2^T)] + resid;  x,y f32; W in type t */
 int anyref_op_gemv(int t, void* stream, const float* x, const float* gain, float eps, const void* W,
                    const void* W2, const float* bias, float* y, const float* resid, int B, int N, int K, int act);
-/* anyref_op_gemv (t = 0 / 1) plus the f32 copy of the RMS-normalised rows the lm_head GEMV writes (needs gain):
+/* anyref_op_gemv (t = 0 / 1 / 2) plus the f32 copy of the RMS-normalised rows the lm_head GEMV writes (needs gain):
  * xn_out[(xn_row_map ? xn_row_map[b] : b) * xn_ld + k], xn_out 16-byte aligned, xn_ld % 4 == 0 */
 int anyref_op_gemv_xn(int t, void* stream, const float* x, const float* gain, float eps, const void* W, const void* W2,
                       const float* bias, float* y, const float* resid, int B, int N, int K, int act, float* xn_out,
                       const int32_t* xn_row_map, int xn_ld);
 /* the model's RoPE table: out_host f32 [S][2][hd/2] = cos | sin of pos * theta^(-2d/hd) (HOST pointer) */
 int anyref_op_rope_table(int S, int hd, float theta, float* out_host);
-/* the decode step's attention as the model runs it (t = 0 f32 / 1 bf16 cache): qkv f32 [B, 3*H*hd], pos i32 [B], cs_tab
+/* the decode step's attention as the model runs it (t = 0 f32 / 1 bf16 / 2 f16 cache): qkv f32 [B, 3*H*hd], pos i32 [B], cs_tab
  * f32 [maxS][2][hd/2]; rotates q, k at pos[b], appends k, v to kc / vc T [B, maxS, H, hd] (and q to q_keep, same
  * layout, if given), out f32 [B, H*hd] = attention over keys [0, pos[b]].  force_fallback = 0: the fused kernel, or
  * the fallback where it refuses; 1: the fallback (RoPE + append, then the generic attention with Sq = 1) */
 int anyref_op_decode_attn(int t, void* stream, const float* qkv, int B, int H, int hd, const int32_t* pos,
                           const float* cs_tab, void* kc, void* vc, int maxS, float scale, float* out, void* q_keep,
                           int force_fallback);
-/* prefill RoPE + KV append (t = 0 f32 / 1 bf16): qkv T [B, S, 3, H, hd], or (slab0 non-NULL) the sum of two f32 slabs of
- * that shape; rows s < lens[b] (all if lens is NULL) go to position pos0[b] + s (pos0 NULL: 0); q_out T [B, S, H, hd],
+/* prefill RoPE + KV append (t = 0 f32 / 1 bf16 / 2 f16): qkv T [B, S, 3, H, hd], or (slab0 non-NULL) the sum of two f32 slabs
+ * of that shape (rounded to T first; t = 0: not rounded); rows s < lens[b] (all if lens is NULL) go to position pos0[b] + s (pos0 NULL: 0); q_out T [B, S, H, hd],
  * kc / vc / q_keep T [B, maxS, H, hd] */
 int anyref_op_rope_cache(int t, void* stream, const void* qkv, const float* slab0, const float* slab1, int B, int S, int H,
                          int hd, const int32_t* pos0, const int32_t* lens, const float* cs_tab, void* q_out, void* kc,
                          void* vc, int maxS, void* q_keep);
 /* argmax of x f32 rows [M, N] (row stride ldx) -> out i64 [M], first index on ties, NaN greatest; pos (optional) += 1.
- * table non-NULL (bf16 if is_bf16 else f32, [vocab, D]): also x_next f32 [M, D] = table[out[b]], row_map[b] =
+ * table non-NULL ([vocab, D]; is_bf16 is its dtype: 0 = f32, 1 = bf16, 2 = f16): also x_next f32 [M, D] = table[out[b]], row_map[b] =
  * b * maxS + pos[b], kvlen[b] = pos[b] + 1 (pos required) */
 int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_t* out, int32_t* pos, const void* table,
                      int is_bf16, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen);

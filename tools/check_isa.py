@@ -5,6 +5,8 @@
     run-to-run different results from a hipGraph replay / beside a second stream on this stack
     (DESIGN.md, "Compiler / runtime hazards")
   * the LDS-DMA GEMM must not wait vmcnt(0) in front of a tile's first ds_read (Makefile note on gemm.o)
+  * the f16 decode GEMV (ANYREF_MODE_PERF_F16) must multiply on the packed f16 dot (v_dot2[c]_f32_f16), not fall back to
+    unpack + FMA
 
 usage: python tools/check_isa.py    (compiles anyref_amd/csrc/*.hip to assembly under /tmp)
 """
@@ -39,6 +41,15 @@ def main():
                         if "s_waitcnt vmcnt(0)" in l and any("ds_read" in x for x in lines[k + 1:k + 4]))
                 if n:
                     print(f"FAIL {src}: {m.group(1)} waits vmcnt(0) before {n} ds_read group(s)")
+                    bad += 1
+        if src == "gemv.hip":
+            f16 = re.findall(r"^(_ZN6anyref11gemv_kernelINS_3f16E\S*):[^\n]*\n(.*?)\.Lfunc_end", s, re.S | re.M)
+            if not f16:
+                print("FAIL gemv.hip: no f16 decode GEMV instantiation found")
+                bad += 1
+            for name, body in f16:
+                if not re.search(r"\bv_dot2c?_f32_f16(_e32|_e64)?\s", body):
+                    print(f"FAIL gemv.hip: {name} has no v_dot2_f32_f16 / v_dot2c_f32_f16 (unpack + FMA fallback)")
                     bad += 1
     print("isa check:", "FAILED" if bad else "ok")
     return 1 if bad else 0
