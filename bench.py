@@ -12,7 +12,13 @@ torch.distributed.run, one rank per GPU) the default is configs[2] (C3: the same
 scaling) and the step ends with the RCCL all-gather of the low-res mask logits + token ids.
 
 The timed region runs what ships: hipGraph replay of the decode step, SAM encoder on the second stream,
-no profiler.  Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+no profiler.  Rank 0 prints ONE JSON line.  A plain run only sets up, warms up, times the steps, writes
+--dump-outputs and prints the line.  With --full the line also carries what takes runs of its own, after
+the timed region:
+  ranks, collective        : (N > 1) every rank's device; the step's all-gathers timed alone
+  kernel_breakdown         : per-kernel table of one eager step
+  mfma_stages              : (C2, N = 1) the MFMA-bound stages alone on the chip
+  secondary, tolerance_mode: (C2, N = 1) the c3-shape / c4 / c5 configurations and the parity16 mode, timed
   roofline     : the dominant kernel of the step (by summed device time), measured in a separate untimed
                  pass of the same step from KERNEL-SIDE timestamps (every workgroup stamps the 100 MHz wall
                  clock at entry / exit; include/anyref_hip.h anyref_stamps_*): in situ (frac) and with the
@@ -78,6 +84,11 @@ def main():
                     help="default: perf (bf16 LLaMA / CLIP, f16 SAM encoder); c5: perf_fp8w; parity16: the tolerance-meeting mode "
                          "(f32 activations as bf16 pairs x exactly stored bf16 weights) as the timed headline")
     ap.add_argument("--batch-per-gpu", type=int, default=None, help="default: 1 (c2 / c4), 4 (c3), 8 (c5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: roofline, kernel breakdown, MFMA stages, "
+                         "N > 1 ranks and collective, and (C2, N = 1) the secondary configurations, the parity16 mode, the CPU "
+                         "baseline and parity.  --roofline-steps, --stamps-out, --no-secondary, --no-cpu-baseline and --no-parity "
+                         "act only with --full")
     ap.add_argument("--roofline-steps", type=int, default=3, help="steps of the untimed kernel-timestamp passes")
     ap.add_argument("--stamps-out", default=None,
                     help="write the per-launch kernel-timestamp table (CSV) here; default gpurun_out/stamps_<config>.csv "
@@ -96,6 +107,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if args.stamps_out and not args.full:
+        ap.error("--stamps-out needs --full (the kernel-timestamp passes run only there)")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -153,9 +166,10 @@ def main():
         log(f"[bench] outputs of the last timed step -> {out_dir}: " +
             ", ".join(f"{k} {list(v.shape)} {v.dtype}" for k, v in files.items()))
 
-    def measure(config, steps, warmup, B=None, mode=None, roofline_steps=3, stamps_out=None, full=True, dump_dir=None):
-        """Build `config`, time `steps` steps of it on the production path, then (untimed) measure its dominant
-        kernel.  -> (result dict, context for the CPU / parity legs)."""
+    def measure(config, steps, warmup, B=None, mode=None, roofline_steps=3, stamps_out=None, full=True, dump_dir=None,
+                untimed=True):
+        """Build `config`, time `steps` steps of it on the production path, then (if `untimed`) measure its dominant
+        kernel in untimed passes.  -> (result dict, context for the CPU / parity legs)."""
         mode = mode or args.mode or ("perf_fp8w" if config == "c5" else "perf")
         B = B or {"c3": 4, "c5": 8}.get(config, 1)
         if config in ("c2", "c3", "c4"):
@@ -228,6 +242,39 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
         ips = n_global * steps / dt
+        workload = {"c2": "C2: LLaVA-7B + CLIP ViT-L/14 + SAM-H refer-seg forward, 1024x1024, S=320 prompt, "
+                          f"{T} new tokens, KV cache",
+                    "c3": f"C3: C2 at {B} images per GPU, batch-sharded data parallel: global batch {B}*N = {n_global} "
+                          f"({B * 8} on 8 GPUs), all-gather of mask logits + ids per step; S=320 prompts, {T} new tokens, KV cache",
+                    "c4": "C4: C2 + audio reference: 3 raw mel clips [1,3,1,128,204] -> ImageBind audio trunk "
+                          f"({'HIP, inside the handle' if args.audio_trunk == 'hip' else 'PyTorch-ROCm module'}) -> "
+                          f"audio_projector -> 3 <audio_ref> slots; S=320 prompt, {T} new tokens, KV cache",
+                    "c5": "C5: 13B LLM + CLIP ViT-L/14 + SAM-H refer-seg forward, fp8-weight LLM, 1024x1024, S=320 "
+                          f"prompt, {T} new tokens, KV cache",
+                    "tiny": "C1 tiny plumbing config"}[config]
+        res = {
+            "metric": {"c2": "images/sec (1024^2, 7B LLM+ViT-L+SAM-H)", "c3": "images/sec (1024^2, 7B LLM+ViT-L+SAM-H)",
+                       "c4": "images/sec (1024^2, 7B LLM+ViT-L+SAM-H, audio-referred: ImageBind audio trunk + 3 audio tokens)",
+                       "c5": "images/sec (1024^2, 13B LLM+ViT-L+SAM-H, fp8 weights)",
+                       "tiny": "images/sec (tiny plumbing config)"}[config],
+            "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": steps, "warmup": warmup,
+            "ms_per_step": round(dt / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": {"perf": "bf16 (LLaMA / CLIP) + f16 (SAM encoder)",
+                      "perf_fp8w": "bf16 (LLaMA / CLIP; LLM linear weights fp8 e4m3, weight-only) + f16 (SAM encoder)",
+                      "parity16": "f32 activations as bf16 pairs x bf16 weights (bf16 MFMA, f32 accumulate); f32 attention"}[mode],
+            "data": "synthetic",
+            "config": {"workload": workload, "batch_per_gpu": B, "global_batch": n_global, "parallelism": f"dp{world}",
+                       "max_new_tokens": T, "weights": "random-init N(0,0.02^2) rounded to bf16",
+                       "launch_path": "hipGraph decode step, SAM encoder on a second stream, profiler off"},
+        }
+        if config == "c2" and T == 10 and mode == "perf" and ids.shape[1] == 65:
+            # SURVEY.md §8d: algorithmic FLOPs of one image (S = 320, T = 10, bf16) x images/s over the dense bf16 MFMA peak
+            res["mfma_frac_e2e"] = round(FLOP_PER_IMAGE_C2 * ips / world / (PEAK_BF16_TFLOPS * 1e12), 4)
+            res["flop_per_image"] = FLOP_PER_IMAGE_C2
+        ctx = dict(cfg=cfg, sd=sd, model=model, clip=clip, sam=sam, ids=ids, sizes=sizes, H=H, W=W, B=B, mode=mode)
+        if not untimed:                                  # a plain run: the headline alone
+            return res, ctx
         # ---- N > 1: who took part, and what the per-step exchange costs (untimed, after the timed region) ----
         ranks_info = collective = None
         if world > 1:
@@ -411,43 +458,13 @@ def main():
                              tflops=round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1),
                              gbs=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)) for k, v in sorted(
             table.items(), key=lambda kv: -kv[1]["ms"])}
-        workload = {"c2": "C2: LLaVA-7B + CLIP ViT-L/14 + SAM-H refer-seg forward, 1024x1024, S=320 prompt, "
-                          f"{T} new tokens, KV cache",
-                    "c3": f"C3: C2 at {B} images per GPU, batch-sharded data parallel: global batch {B}*N = {n_global} "
-                          f"({B * 8} on 8 GPUs), all-gather of mask logits + ids per step; S=320 prompts, {T} new tokens, KV cache",
-                    "c4": "C4: C2 + audio reference: 3 raw mel clips [1,3,1,128,204] -> ImageBind audio trunk "
-                          f"({'HIP, inside the handle' if args.audio_trunk == 'hip' else 'PyTorch-ROCm module'}) -> "
-                          f"audio_projector -> 3 <audio_ref> slots; S=320 prompt, {T} new tokens, KV cache",
-                    "c5": "C5: 13B LLM + CLIP ViT-L/14 + SAM-H refer-seg forward, fp8-weight LLM, 1024x1024, S=320 "
-                          f"prompt, {T} new tokens, KV cache",
-                    "tiny": "C1 tiny plumbing config"}[config]
-        res = {
-            "metric": {"c2": "images/sec (1024^2, 7B LLM+ViT-L+SAM-H)", "c3": "images/sec (1024^2, 7B LLM+ViT-L+SAM-H)",
-                       "c4": "images/sec (1024^2, 7B LLM+ViT-L+SAM-H, audio-referred: ImageBind audio trunk + 3 audio tokens)",
-                       "c5": "images/sec (1024^2, 13B LLM+ViT-L+SAM-H, fp8 weights)",
-                       "tiny": "images/sec (tiny plumbing config)"}[config],
-            "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": steps, "warmup": warmup,
-            "ms_per_step": round(dt / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"perf": "bf16 (LLaMA / CLIP) + f16 (SAM encoder)",
-                      "perf_fp8w": "bf16 (LLaMA / CLIP; LLM linear weights fp8 e4m3, weight-only) + f16 (SAM encoder)",
-                      "parity16": "f32 activations as bf16 pairs x bf16 weights (bf16 MFMA, f32 accumulate); f32 attention"}[mode],
-            "data": "synthetic",
-            "config": {"workload": workload, "batch_per_gpu": B, "global_batch": n_global, "parallelism": f"dp{world}",
-                       "max_new_tokens": T, "weights": "random-init N(0,0.02^2) rounded to bf16",
-                       "launch_path": "hipGraph decode step, SAM encoder on a second stream, profiler off"},
-            "roofline": roofline,
-        }
+        res["roofline"] = roofline
         if ranks_info is not None:
             res["ranks"] = ranks_info
             res["distinct_devices"] = len({(r["device_uuid"], r["pci_bus"]) for r in ranks_info})
             res["collective"] = collective
         if full:
             res["kernel_breakdown"] = breakdown
-        if config == "c2" and T == 10 and mode == "perf" and ids.shape[1] == 65:
-            # SURVEY.md §8d: algorithmic FLOPs of one image (S = 320, T = 10, bf16) x images/s over the dense bf16 MFMA peak
-            res["mfma_frac_e2e"] = round(FLOP_PER_IMAGE_C2 * ips / world / (PEAK_BF16_TFLOPS * 1e12), 4)
-            res["flop_per_image"] = FLOP_PER_IMAGE_C2
         if full and config == "c2" and world == 1 and B == 1 and mode == "perf":
             # untimed: the MFMA-bound stages alone (no co-running stream), against the dense bf16 / f16 MFMA peak;
             # algorithmic FLOPs from SURVEY.md §8d (S = 320 prompt)
@@ -468,18 +485,17 @@ def main():
                                           frac_of_mfma_peak=round(fl / ms / 1e9 / PEAK_BF16_TFLOPS, 4)) for k, (ms, fl) in st.items()}
             res["mfma_stages"]["note"] = ("each stage alone on the chip through its C-ABI entry (sam_encode / llm_forward / encode_images, "
                                           "5 calls after 2 warm-ups, host-timed); SAM encoder operands f16, LLaMA / CLIP bf16")
-        ctx = dict(cfg=cfg, sd=sd, model=model, clip=clip, sam=sam, ids=ids, sizes=sizes, H=H, W=W, B=B, mode=mode)
         return res, ctx
 
     res, ctx = measure(args.config, args.steps, args.warmup, B=args.batch_per_gpu, roofline_steps=args.roofline_steps,
-                       stamps_out=args.stamps_out, dump_dir=args.dump_outputs)
+                       stamps_out=args.stamps_out, dump_dir=args.dump_outputs, untimed=args.full)
     if args.config in ("c4", "c5", "c3"):
         args.no_cpu_baseline = True      # the CPU baseline / parity legs are quoted on C2 (13B fp32 needs ~55 GB of host memory)
     cfg, sd, model, clip, sam, ids, sizes, H, W = (ctx[k] for k in ("cfg", "sd", "model", "clip", "sam", "ids", "sizes", "H", "W"))
     mode = ctx["mode"]
 
     # ---- driver-visible secondary lines (N = 1, headline config only): the other single-GPU configurations, short ----
-    if world == 1 and args.config == "c2" and not args.no_secondary and os.environ.get("ANYREF_BENCH_SECONDARY", "1") != "0":
+    if args.full and world == 1 and args.config == "c2" and not args.no_secondary and os.environ.get("ANYREF_BENCH_SECONDARY", "1") != "0":
         log("[bench] GPU leg: " + json.dumps({k: res[k] for k in ("value", "ms_per_step", "roofline")}))
         secondary = {}
         import gc
@@ -502,7 +518,7 @@ def main():
     # storage, every activation that feeds a matrix product carried as a pair of bf16 terms (2^-18 relative), f32
     # attention operands; its parity numbers (fan-in workload, where the bar bites) are attached below from `parity`
     tol = None
-    if world == 1 and args.config == "c2" and mode != "parity16" and os.environ.get("ANYREF_BENCH_TOLERANCE", "1") != "0":
+    if args.full and world == 1 and args.config == "c2" and mode != "parity16" and os.environ.get("ANYREF_BENCH_TOLERANCE", "1") != "0":
         try:
             m16 = AnyRefForCausalLM.from_state_dict(cfg, sd, mode="parity16", device=local, max_batch=ctx["B"], max_seg=2)
             m16.config.eos_token_id = None
@@ -530,7 +546,7 @@ def main():
         log("[bench] tolerance mode: " + json.dumps(tol))
 
     # ---------------- CPU baseline + parity against it (rank 0, N=1 only) ----------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import anyref_oracle as O
         from oracle.check import compare_generate, summarize
         # the GPU box gives one GPU a share of 16 host cores (of 256 visible); oversubscribing them

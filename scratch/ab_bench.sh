@@ -8,7 +8,7 @@ cp "$OLD" /tmp/lib_old.so
 for r in $(seq 1 $R); do
   for w in old new; do
     cp /tmp/lib_$w.so anyref_amd/libanyref_hip.so
-    python bench.py --no-cpu-baseline --no-parity --steps 10 "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-parity --steps 10 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$w', d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('isolated', {}).get('frac'))"

@@ -90,11 +90,11 @@ def test_two_ranks_one_gpu_equal_single_process(tmp_path):
 
 
 def test_bench_two_ranks_same_device_smoke():
-    """`bench.py --gpus 2` end to end (tiny config, gloo, both ranks on cuda:0): one JSON line, aggregate over 2 ranks"""
+    """`bench.py --gpus 2 --full` end to end (tiny config, gloo, both ranks on cuda:0): one JSON line, aggregate over 2 ranks"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(34500 + os.getpid() % 2000), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--config", "tiny", "--dist-backend", "gloo", "--same-device"]
+           "--warmup", "1", "--config", "tiny", "--dist-backend", "gloo", "--same-device", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
