@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(HERE, "libanyref_hip.so")
 
 ABI_VERSION = 2
 F32, BF16, F16 = 0, 1, 2
-MODE_PARITY, MODE_PERF, MODE_PERF_FP8W, MODE_PARITY16, MODE_PERF_F16 = 0, 1, 2, 3, 4
+MODE_PARITY, MODE_PERF, MODE_PERF_FP8W, MODE_PARITY16, MODE_PERF_F16, MODE_PARITY16_F16 = 0, 1, 2, 3, 4, 5
 
 
 class AnyrefConfig(C.Structure):
@@ -100,6 +100,7 @@ SYMBOLS = {
     "anyref_op_clip_finish": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
     "anyref_op_gemv": (_I, [_I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "anyref_op_gemv_xn": (_I, [_I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I]),
+    "anyref_op_split_roundtrip": (_I, [_I, _P, _P, _P, _P, _I, _I]),
     "anyref_op_rope_table": (_I, [_I, _I, _F, _P]),
     "anyref_op_decode_attn": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _I]),
     "anyref_op_rope_cache": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),

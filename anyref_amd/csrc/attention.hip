@@ -649,6 +649,8 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, const int bx, const
         reinterpret_cast<uint16_t*>(Ob)[c + 1] = from_f32<T>(v[1]).x;
         reinterpret_cast<uint16_t*>(Ob)[c + 2] = from_f32<T>(v[2]).x;
         reinterpret_cast<uint16_t*>(Ob)[c + 3] = from_f32<T>(v[3]).x;
+      } else if (a.o_split == 2) {  // split-pair rows with f16 terms (ANYREF_MODE_PARITY16_F16)
+        st4<sp16h>(reinterpret_cast<sp16h*>(a.O) + (int64_t)b * a.o_bs + (int64_t)iq * a.o_rs, (int)(h * a.o_hs) + c, v[0], v[1], v[2], v[3]);
       } else if (a.o_split) {  // split-pair rows (the proj / o_proj GEMM's A operand in ANYREF_MODE_PARITY16)
         st4<sp16>(reinterpret_cast<sp16*>(a.O) + (int64_t)b * a.o_bs + (int64_t)iq * a.o_rs, (int)(h * a.o_hs) + c, v[0], v[1], v[2], v[3]);
       } else {
@@ -1167,7 +1169,9 @@ __device__ __forceinline__ void attn_sp_body(const AttnArgs& a, const int bx, co
     for (int d = 0; d < DB; ++d) {
       const float4v v = ot[d] * inv;
       const int c = d * 16 + 4 * g;
-      if (a.o_split)
+      if (a.o_split == 2)  // f16 terms (ANYREF_MODE_PARITY16_F16); the products above are bf16 pairs in both modes
+        st4<sp16h>(reinterpret_cast<sp16h*>(a.O) + (int64_t)b * a.o_bs + (int64_t)iq * a.o_rs, (int)(h * a.o_hs) + c, v[0], v[1], v[2], v[3]);
+      else if (a.o_split)
         st4<sp16>(reinterpret_cast<sp16*>(a.O) + (int64_t)b * a.o_bs + (int64_t)iq * a.o_rs, (int)(h * a.o_hs) + c, v[0], v[1], v[2], v[3]);
       else
         *reinterpret_cast<float4v*>(Obf + c) = v;
@@ -1292,6 +1296,7 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(AttnArgs a, int HD) {
   const float v = l > 0.f ? o / l : 0.f;
   const int64_t off = (int64_t)b * a.o_bs + (int64_t)h * a.o_hs + (int64_t)iq * a.o_rs + d;
   if (a.o_f32) reinterpret_cast<float*>(a.O)[off] = v;
+  else if (a.o_split == 2) st1<sp16h>(reinterpret_cast<sp16h*>(a.O) + (int64_t)b * a.o_bs + (int64_t)iq * a.o_rs, (int)(h * a.o_hs) + d, v);
   else if (a.o_split) st1<sp16>(reinterpret_cast<sp16*>(a.O) + (int64_t)b * a.o_bs + (int64_t)iq * a.o_rs, (int)(h * a.o_hs) + d, v);
   else reinterpret_cast<T*>(a.O)[off] = from_f32<T>(v);
 }

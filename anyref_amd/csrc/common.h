@@ -123,6 +123,14 @@ __device__ inline uint32_t pack2_from_f32(float lo, float hi) {
 struct sp16 {
   uint32_t x;
 };
+// ---- split-pair activations with f16 terms (ANYREF_MODE_PARITY16_F16) -----------------------------
+// Same row layout, hi = f16(a) and lo = f16(a - hi): |a - hi - lo| <= max(2^-22 |a|, 2^-25) while |a| <= 65504 (past that hi
+// is inf).  The weights are f16 as an fp16 checkpoint stores them, so nothing is rounded at finalize, and an f16 weight
+// times an f16 term (11 + 11 bits) is exact in the f32 accumulator like the bf16 product above.  lo is an f16 SUBNORMAL
+// whenever |a| < ~2^-3: the kernels are built without flush-denormals and the f16 MFMA keeps them.
+struct sp16h {
+  uint32_t x;
+};
 template <typename T>
 struct is_split {
   static constexpr bool value = false;
@@ -131,6 +139,23 @@ template <>
 struct is_split<sp16> {
   static constexpr bool value = true;
 };
+template <>
+struct is_split<sp16h> {
+  static constexpr bool value = true;
+};
+// the 16-bit type of a pair's two terms = the type of the weights it multiplies (any other T: itself)
+template <typename T>
+struct split_term {
+  using type = T;
+};
+template <>
+struct split_term<sp16> {
+  using type = bf16;
+};
+template <>
+struct split_term<sp16h> {
+  using type = f16;
+};
 // bf16 index (inside the row) of the hi term of logical column c; the lo term sits 64 elements further
 __host__ __device__ inline int sp_col(int c) { return ((c >> 6) << 7) + (c & 63); }
 __device__ inline void sp_split(float v, uint16_t& hi, uint16_t& lo) {
@@ -138,9 +163,21 @@ __device__ inline void sp_split(float v, uint16_t& hi, uint16_t& lo) {
   hi = h.x;
   lo = f2bf(v - bf2f(h)).x;
 }
-__device__ inline float sp_load(const sp16* row, int c) {
-  const bf16* p = reinterpret_cast<const bf16*>(row) + sp_col(c);
-  return bf2f(p[0]) + bf2f(p[64]);
+template <typename E>  // E: term type (bf16 / f16)
+__device__ inline void sp_split_t(float v, uint16_t& hi, uint16_t& lo) {
+  if constexpr (is_half16<E>::value) {
+    const f16 h = f2h(v);
+    hi = h.x;
+    lo = f2h(v - h2f(h)).x;
+  } else {
+    sp_split(v, hi, lo);
+  }
+}
+template <typename T>
+__device__ inline float sp_load(const T* row, int c) {
+  using E = typename split_term<T>::type;
+  const E* p = reinterpret_cast<const E*>(row) + sp_col(c);
+  return to_f32<E>(p[0]) + to_f32<E>(p[64]);
 }
 
 // Typed row stores: `row` points at the first element of a matrix row, c is the logical column.
@@ -149,7 +186,7 @@ __device__ inline void st1(T* row, int c, float v) {
   if constexpr (is_split<T>::value) {
     uint16_t* p = reinterpret_cast<uint16_t*>(row) + sp_col(c);
     uint16_t h, l;
-    sp_split(v, h, l);
+    sp_split_t<typename split_term<T>::type>(v, h, l);
     p[0] = h;
     p[64] = l;
   } else {
@@ -161,8 +198,8 @@ __device__ inline void st2(T* row, int c, float a, float b) {  // c % 2 == 0
   if constexpr (is_split<T>::value) {
     uint16_t* p = reinterpret_cast<uint16_t*>(row) + sp_col(c);
     uint16_t h0, l0, h1, l1;
-    sp_split(a, h0, l0);
-    sp_split(b, h1, l1);
+    sp_split_t<typename split_term<T>::type>(a, h0, l0);
+    sp_split_t<typename split_term<T>::type>(b, h1, l1);
     *reinterpret_cast<uint32_t*>(p) = (uint32_t)h0 | ((uint32_t)h1 << 16);
     *reinterpret_cast<uint32_t*>(p + 64) = (uint32_t)l0 | ((uint32_t)l1 << 16);
   } else if constexpr (sizeof(T) == 2) {
@@ -178,10 +215,10 @@ __device__ inline void st4(T* row, int c, float a, float b, float cc, float d) {
     typedef uint32_t u2 __attribute__((ext_vector_type(2)));
     uint16_t* p = reinterpret_cast<uint16_t*>(row) + sp_col(c);
     uint16_t h[4], l[4];
-    sp_split(a, h[0], l[0]);
-    sp_split(b, h[1], l[1]);
-    sp_split(cc, h[2], l[2]);
-    sp_split(d, h[3], l[3]);
+    sp_split_t<typename split_term<T>::type>(a, h[0], l[0]);
+    sp_split_t<typename split_term<T>::type>(b, h[1], l[1]);
+    sp_split_t<typename split_term<T>::type>(cc, h[2], l[2]);
+    sp_split_t<typename split_term<T>::type>(d, h[3], l[3]);
     *reinterpret_cast<u2*>(p) = u2{(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16)};
     *reinterpret_cast<u2*>(p + 64) = u2{(uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16)};
   } else {

@@ -54,6 +54,11 @@ struct Mma<sp16> {  // split-pair activations: the LDS-DMA kernel only (bf16 MFM
   static constexpr int VEC = 8;
 };
 template <>
+struct Mma<sp16h> {  // the same with f16 terms against f16 weights (f16 MFMA)
+  static constexpr int KS = 32;
+  static constexpr int VEC = 8;
+};
+template <>
 struct Mma<float> {
   static constexpr int KS = 4;
   static constexpr int VEC = 4;
@@ -243,8 +248,8 @@ __device__ __forceinline__ void gemm_epilogue_ct(const GemmArgs& a, float4v (&ac
                     uint16_t h[8], l[8];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                      sp_split(vv[j][e], h[e], l[e]);
-                      sp_split(vv[j | 1][e], h[4 + e], l[4 + e]);
+                      sp_split_t<typename split_term<T>::type>(vv[j][e], h[e], l[e]);
+                      sp_split_t<typename split_term<T>::type>(vv[j | 1][e], h[4 + e], l[4 + e]);
                     }
                     *reinterpret_cast<uint4v*>(p) = uint4v{(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16),
                                                            (uint32_t)h[4] | ((uint32_t)h[5] << 16), (uint32_t)h[6] | ((uint32_t)h[7] << 16)};
@@ -450,7 +455,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
   // against K/64 tiles of the bf16 weight (W tile = A tile >> 1, re-fetched from L2 for the lo pass); the epilogue
   // writes f32 or a split pair again.  ET: element type of both operand tiles and of the MFMA.
   constexpr bool SPLIT = is_split<TT>::value;
-  using ET = std::conditional_t<SPLIT, bf16, TT>;
+  using ET = typename split_term<TT>::type;  // (sp16: bf16, sp16h: f16)
   constexpr int AX = SPLIT ? 2 : 1;  // 16-bit elements per logical A element
   static_assert(!W8 || !(is_half16<T>::value || SPLIT), "fp8 weights are widened to bf16");
   constexpr int BK = 64, NW = WM * WN;
@@ -871,7 +876,7 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   if constexpr (SP) {
     if (a.K % 64 || a.lda % 64 || a.sA % 64 || a.w_fp8 || (!a.c_f32 && !a.slabs_out && (a.ldc % 64 || a.sC % 64)) ||
         (a.norm_out && a.norm_ld % 64))
-      throw std::runtime_error("gemm<sp16>: K, lda, the A batch stride (and ldc of a split-pair output) must be multiples of 64");
+      throw std::runtime_error("gemm<sp16 / sp16h>: K, lda, the A batch stride (and ldc of a split-pair output) must be multiples of 64");
   }
   if (a.slabs_out && a.slabs > 1) {  // raw split-K: the consumer sums the slices
     if (!IS16 || a.batch != 1 || a.row_map || a.bias || a.resid || a.act != ACT_NONE || a.swiglu_pairs || a.w_fp8 ||
@@ -1019,10 +1024,10 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
           gm = gm < 1 ? 1 : (gm > tiles_m ? tiles_m : gm);
           a.group_m = knobs().gm >= 0 ? knobs().gm : gm;
         }
-        // gemm_bf16_... -> gemm_f16_... / gemm_sp16_...; "_dec": at most 16 rows (the MFMA decode path: HBM-bound weight streaming,
+        // gemm_bf16_... -> gemm_f16_... / gemm_sp16_... / gemm_sp16h_...; "_dec": at most 16 rows (the MFMA decode path: HBM-bound weight streaming,
         // booked apart from the MFMA-bound prefill launches of the same tile)
         char tagt[56];
-        snprintf(tagt, sizeof(tagt), "%s%s%s", SP ? "gemm_sp16_" : is_half16<T>::value ? "gemm_f16_" : "gemm_bf16_", tag + 10,
+        snprintf(tagt, sizeof(tagt), "%s%s%s", SP ? (is_half16<typename split_term<T>::type>::value ? "gemm_sp16h_" : "gemm_sp16_") : is_half16<T>::value ? "gemm_f16_" : "gemm_bf16_", tag + 10,
                  a.M <= 16 ? "_dec" : "");
         ProfScope prof(tagt, flops, bytes, s);
         dim3 grid(cdiv(a.N, BN) * cdiv(a.M, BM), 1, a.batch);

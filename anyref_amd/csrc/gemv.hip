@@ -41,8 +41,9 @@ template <typename T, int NB, bool DUAL, int XPT, bool W8 = false, bool PAIR = f
 __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
   static_assert(!W8 || std::is_same<T, bf16>::value, "fp8 weights go with bf16 activations");
   // T = sp16 (ANYREF_MODE_PARITY16): bf16 weights, exactly as stored, against the f32 activation row kept in LDS as f32
-  // (16 - 44 KB) -- same bytes per decode step as the bf16 mode, f32 products and sums
-  using WE = std::conditional_t<is_split<T>::value, bf16, T>;   // weight element
+  // (16 - 44 KB) -- same bytes per decode step as the bf16 mode, f32 products and sums.  T = sp16h (ANYREF_MODE_PARITY16_F16):
+  // the same with f16 weights
+  using WE = typename split_term<T>::type;                      // weight element (sp16: bf16, sp16h: f16)
   using XE = std::conditional_t<is_split<T>::value, float, T>;  // staged activation element
   using WT = std::conditional_t<W8, uint8_t, WE>;
   constexpr int VN = W8 ? 16 : Vec16<WE>::N;  // weights per 16-byte load
@@ -699,7 +700,7 @@ static void gemv_dispatch(const GemvArgs& a_in, int b0, int nb, hipStream_t s) {
     // one tag per kernel instantiation, so a tag's average can be checked against rocprofv3's per-kernel one
     char tag[40];
     snprintf(tag, sizeof(tag), "gemv_%s%s_x%d",
-             a.w_fp8 ? "fp8w" : (is_split<T>::value ? "sp16" : is_half16<T>::value ? "f16" : sizeof(T) == 2 ? "bf16" : "f32"),
+             a.w_fp8 ? "fp8w" : (is_split<T>::value ? (is_half16<typename split_term<T>::type>::value ? "sp16h" : "sp16") : is_half16<T>::value ? "f16" : sizeof(T) == 2 ? "bf16" : "f32"),
              a.W2 ? "_swiglu" : "", XPT);
     ProfScope prof(tag, 2.0 * nb * a.N * (double)a.K * (a.W2 ? 2 : 1), wbytes, s);
     if (g_stamp && g_stamp->on) a.stamp = g_stamp->slot(tag, wbytes, grid);
@@ -742,7 +743,7 @@ static void gemv_dispatch(const GemvArgs& a_in, int b0, int nb, hipStream_t s) {
 
 template <typename T>
 void launch_gemv(const GemvArgs& a, hipStream_t s) {
-  const int VN = a.w_fp8 ? 16 : Vec16<std::conditional_t<is_split<T>::value, bf16, T>>::N;
+  const int VN = a.w_fp8 ? 16 : Vec16<typename split_term<T>::type>::N;
   if (a.K % VN || ((uintptr_t)a.W & 15)) throw std::runtime_error("gemv: K must be a multiple of 16 bytes");
   if (a.w_fp8 && (!std::is_same<T, bf16>::value || !a.wscale || (a.W2 && !a.wscale2)))
     throw std::runtime_error("gemv: fp8 weights need the bf16 mode and per-row scales");
@@ -797,6 +798,7 @@ void launch_gemv_skinny_f32(const GemvArgs& a, hipStream_t s) {
 }
 template void launch_gemv<bf16>(const GemvArgs&, hipStream_t);
 template void launch_gemv<sp16>(const GemvArgs&, hipStream_t);
+template void launch_gemv<sp16h>(const GemvArgs&, hipStream_t);
 template void launch_gemv<f16>(const GemvArgs&, hipStream_t);
 
 }  // namespace anyref

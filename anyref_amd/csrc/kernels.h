@@ -267,6 +267,7 @@ struct AttnArgs {
   int o_f32 = 0;  // 1: O is f32 instead of T (decode step feeds the f32 GEMV)
   // 1 (T = float only): O is a split-pair matrix (common.h sp16: the A operand of the GEMM that follows in
   // ANYREF_MODE_PARITY16); o_bs / o_rs are whole matrix rows (multiples of 64 elements), o_hs % 4 == 0
+  // 2: the same with f16 terms (sp16h, ANYREF_MODE_PARITY16_F16) -- only the output store differs
   int o_split = 0;
   // 1 (T = float only, head dim 64 / 80 / 128): the f32 operands are multiplied as bf16 PAIRS on the 16-bit MFMA (three
   // passes per product, attention.hip attn_sp_body) instead of the f32 MFMA -- same f32-level result at 3/16 of the MFMA time
@@ -326,8 +327,9 @@ void launch_im2col_3x3(const void* in, int B, int g, int C, void* out, hipStream
 template <typename T>
 void launch_convert(const float* in, int64_t ld_in, void* out, int64_t ld_out, int rows, int cols,
                     hipStream_t s, unsigned long long* counts = nullptr);
-// split-pair (sp16) rows -> f32: out[r, c] = hi + lo; ld_in in sp16 elements (a multiple of 64)
-void launch_unsplit(const void* in, int64_t ld_in, float* out, int64_t ld_out, int rows, int cols, hipStream_t s);
+// split-pair (sp16; f16_terms: sp16h) rows -> f32: out[r, c] = hi + lo; ld_in in pair elements (a multiple of 64)
+void launch_unsplit(const void* in, int64_t ld_in, float* out, int64_t ld_out, int rows, int cols, hipStream_t s,
+                    int f16_terms = 0);
 // out[m, :] = a[m, :] + b[m % bmod, :]   (f32; position embeddings, keys+pe ...)
 void launch_add_rows(const float* a, const float* b, int bmod, float* out, int M, int D, hipStream_t s);
 template <typename T>

@@ -114,7 +114,8 @@ void ModelBase::drop_raw() {
 constexpr int kRowPadBytes = 128;  // see Lin::ld
 // Storage roles of an arithmetic mode.  T names the GEMM A-operand (activation) type; W is what the weights are packed as,
 // Q what the attention kernels read (q / k / v rows, the KV cache).  float / bf16 / f16: all three are T.  sp16
-// (ANYREF_MODE_PARITY16): activations as split bf16 pairs, weights bf16 exactly as stored, attention operands f32.
+// (ANYREF_MODE_PARITY16): activations as split bf16 pairs, weights bf16 exactly as stored, attention operands f32.  sp16h
+// (ANYREF_MODE_PARITY16_F16): the same with f16 pairs against f16 weights.
 template <typename T>
 struct ModeTypes {
   using W = T;
@@ -123,6 +124,11 @@ struct ModeTypes {
 template <>
 struct ModeTypes<sp16> {
   using W = bf16;
+  using Q = float;
+};
+template <>
+struct ModeTypes<sp16h> {
+  using W = f16;
   using Q = float;
 };
 template <typename T>
@@ -165,6 +171,10 @@ class Model : public ModelBase {
   static constexpr bool IS16 = sizeof(T) == 2 || SPT;    // the 16-bit MFMA paths (bf16 or split pairs)
   static constexpr bool IS16S = sizeof(TS) == 2 || SPS;
   // the q / k / v projections write the attention operand type: f32 in the f32 and the split-pair modes
+  // AttnArgs::o_split of a pair-typed attention output: 1 = bf16 terms, 2 = f16 terms
+  static constexpr int OSPT = SPT ? (std::is_same<T, sp16h>::value ? 2 : 1) : 0, OSPS = SPS ? (std::is_same<TS, sp16h>::value ? 2 : 1) : 0;
+  // f16 weight storage handed an element past +-65504 fails finalize (check_f16_range)
+  static constexpr bool F16W = std::is_same<T, f16>::value || std::is_same<T, sp16h>::value;
   static constexpr bool QF32 = std::is_same<Q, float>::value, QF32S = std::is_same<QS, float>::value;
   // row stride of an A-operand matrix with `k` logical columns: split-pair rows are whole 64-column blocks
   template <typename E>
@@ -200,6 +210,7 @@ class Model : public ModelBase {
       if (e) (void)hipEventDestroy(e);
   }
   const char* mode_name() const override {
+    if (std::is_same<T, sp16h>::value) return "f32 activations as f16 pairs x f16 weights";
     if (SPT) return "f32 activations as bf16 pairs x bf16 weights";
     if (is_half16<T>::value) return "f16";
     return sizeof(T) == 2 ? (fp8w_ ? (is_half16<TS>::value ? "bf16+fp8w, SAM f16" : "bf16+fp8w")
@@ -599,10 +610,10 @@ E* Model<T, TS>::pack_rows(E* dst, int dst_row0, const std::string& name, int ro
     throw std::runtime_error("shape mismatch for " + name + ": expected " + std::to_string(rows) + "x" +
                              std::to_string(cols) + ", got " + std::to_string(t.numel()) + " elements");
   launch_convert<E>(t.p, cols, dst + (int64_t)dst_row0 * kpad, kpad, rows, cols, 0, weight_counts());
-  if constexpr (std::is_same<T, f16>::value) check_f16_range(name);
+  if constexpr (F16W) check_f16_range(name);
   return dst;
 }
-// ANYREF_MODE_PERF_F16: a weight past f16's range (|w| > 65504) would be stored as inf and turn the outputs into NaN
+// ANYREF_MODE_PERF_F16 / ANYREF_MODE_PARITY16_F16: a weight past f16's range (|w| > 65504) would be stored as inf and turn the outputs into NaN
 template <typename T, typename TS>
 void Model<T, TS>::check_f16_range(const std::string& name) {
   unsigned long long n = 0;
@@ -905,7 +916,7 @@ void Model<T, TS>::finalize() {
       neck2_.k = 9 * C;
       neck2_.w = talloc<WS>(r.size());
       launch_convert<WS>(rf, 9 * C, neck2_.w, 9 * C, C, 9 * C, 0, weight_counts());
-      if constexpr (std::is_same<T, f16>::value) check_f16_range(p + "neck.2.weight");
+      if constexpr (F16W) check_f16_range(p + "neck.2.weight");
       HIP_TRY(hipStreamSynchronize(0));
       dfree(rf);
     }
@@ -1234,7 +1245,7 @@ void Model<T, TS>::clip_tower(hipStream_t s, const float* images, int B) {
     a.o_bs = (int64_t)S * Dc; a.o_rs = Dc; a.o_hs = hd;
     a.B = B; a.H = c.clip_heads; a.Sq = S; a.Sk = S; a.hd = hd;
     a.scale = 1.f / sqrtf((float)hd);
-    a.o_split = SPT; a.sp16 = SPT;
+    a.o_split = OSPT; a.sp16 = SPT;
     launch_attention<Q>(a, s);
     // the two LayerNorms of a block ride on the split-K reductions of the GEMMs in front of them (perf mode)
     if (!gemm(s, c_att_, Dc, L.out, c_x_, Dc, R, ACT_NONE, true, c_x_, Dc, nullptr, &L.ln2, c_h_, false, c.clip_eps))
@@ -1289,7 +1300,7 @@ void Model<T, TS>::audio_encode(hipStream_t s, const float* mel, int n, float* e
     a.o_bs = (int64_t)RS * D; a.o_rs = D; a.o_hs = hd;
     a.B = n; a.H = nh; a.Sq = St; a.Sk = St + 1; a.hd = hd;
     a.scale = 1.f / sqrtf((float)hd);
-    a.o_split = SPT; a.sp16 = SPT;
+    a.o_split = OSPT; a.sp16 = SPT;
     launch_attention<Q>(a, s);
     gemm(s, a_att_, D, Bk.out, a_x_, D, R, ACT_NONE, true, a_x_, D);
     norm(s, a_x_, D, Bk.ln2, a_h_, D, R, D, 1e-6f, false);
@@ -1349,7 +1360,7 @@ void Model<T, TS>::llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev
     a.B = B; a.H = nh; a.Sq = Sp; a.Sk = Sp; a.hd = hd;
     a.scale = 1.f / sqrtf((float)hd);
     a.causal = 1; a.kv_len = lens_dev; a.q_len = lens_dev;
-    a.o_split = SPT; a.sp16 = SPT;
+    a.o_split = OSPT; a.sp16 = SPT;
     launch_attention<Q>(a, s);
     if (!gemm(s, l_att_, H, L.o, l_x_, H, R, ACT_NONE, true, l_x_, H, nullptr, &L.post_norm, l_h_))
       norm(s, l_x_, H, L.post_norm, l_h_, H, R, H, c.llm_rms_eps, false, true);
@@ -1495,7 +1506,7 @@ void Model<T, TS>::sam_encoder(hipStream_t s, const float* images, int B, float*
     a.q_rs = a.k_rs = a.v_rs = 3 * D; a.o_rs = D;
     a.H = nh; a.hd = hd; a.scale = 1.f / sqrtf((float)hd);
     a.Q = s_qkv_; a.K = s_qkv_ + D; a.V = s_qkv_ + 2 * D; a.O = s_att_;
-    a.o_split = SPS; a.sp16 = SPS;
+    a.o_split = OSPS; a.sp16 = SPS;
     // decomposed rel-pos bias: P = q . [rel_pos_h | rel_pos_w]^T for every head in ONE batched MFMA GEMM
     // (batch = heads, A = the q columns of the fused qkv buffer); the attention kernel applies the shift.
     auto rel_gemm = [&](int rows) {
@@ -2171,6 +2182,7 @@ std::unique_ptr<ModelBase> make_model(const anyref_config& cfg, int device) {
     if (sam_bf16) return std::unique_ptr<ModelBase>(new Model<bf16, bf16>(cfg, device));
     return std::unique_ptr<ModelBase>(new Model<bf16, f16>(cfg, device));
   }
+  if (cfg.mode == ANYREF_MODE_PARITY16_F16) return std::unique_ptr<ModelBase>(new Model<sp16h, sp16h>(cfg, device));
   if (cfg.mode == ANYREF_MODE_PERF_F16) return std::unique_ptr<ModelBase>(new Model<f16, f16>(cfg, device));
   throw std::runtime_error("unknown mode");
 }

@@ -403,6 +403,7 @@ template void launch_norm<float>(const NormArgs&, hipStream_t);
 template void launch_norm<bf16>(const NormArgs&, hipStream_t);
 template void launch_norm<f16>(const NormArgs&, hipStream_t);
 template void launch_norm<sp16>(const NormArgs&, hipStream_t);
+template void launch_norm<sp16h>(const NormArgs&, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // im2col
@@ -438,6 +439,7 @@ template void launch_im2col_patch<float>(const float*, int, int, int, void*, int
 template void launch_im2col_patch<bf16>(const float*, int, int, int, void*, int, hipStream_t);
 template void launch_im2col_patch<f16>(const float*, int, int, int, void*, int, hipStream_t);
 template void launch_im2col_patch<sp16>(const float*, int, int, int, void*, int, hipStream_t);
+template void launch_im2col_patch<sp16h>(const float*, int, int, int, void*, int, hipStream_t);
 
 template <typename T>
 __global__ void im2col_3x3_kernel(const T* __restrict__ in, int B, int g, int C, T* __restrict__ out) {
@@ -474,6 +476,7 @@ template void launch_im2col_3x3<float>(const void*, int, int, int, void*, hipStr
 template void launch_im2col_3x3<bf16>(const void*, int, int, int, void*, hipStream_t);
 template void launch_im2col_3x3<f16>(const void*, int, int, int, void*, hipStream_t);
 template void launch_im2col_3x3<sp16>(const void*, int, int, int, void*, hipStream_t);
+template void launch_im2col_3x3<sp16h>(const void*, int, int, int, void*, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // converts / adds
@@ -519,9 +522,11 @@ template void launch_convert<float>(const float*, int64_t, void*, int64_t, int, 
 template void launch_convert<bf16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t, unsigned long long*);
 template void launch_convert<f16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t, unsigned long long*);
 template void launch_convert<sp16>(const float*, int64_t, void*, int64_t, int, int, hipStream_t, unsigned long long*);
+template void launch_convert<sp16h>(const float*, int64_t, void*, int64_t, int, int, hipStream_t, unsigned long long*);
 
-// split-pair rows back to f32 (tests, and wherever an f32 view of an sp16 matrix is needed): out[r, c] = hi + lo
-__global__ void unsplit_kernel(const sp16* __restrict__ in, int64_t ld_in, float* __restrict__ out, int64_t ld_out,
+// split-pair rows back to f32 (tests, and wherever an f32 view of an sp16 / sp16h matrix is needed): out[r, c] = hi + lo
+template <typename T>
+__global__ void unsplit_kernel(const T* __restrict__ in, int64_t ld_in, float* __restrict__ out, int64_t ld_out,
                                int rows, int cols) {
   const int64_t total = (int64_t)rows * cols;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -529,12 +534,16 @@ __global__ void unsplit_kernel(const sp16* __restrict__ in, int64_t ld_in, float
     out[r * ld_out + c] = sp_load(in + r * ld_in, (int)c);
   }
 }
-void launch_unsplit(const void* in, int64_t ld_in, float* out, int64_t ld_out, int rows, int cols, hipStream_t s) {
+void launch_unsplit(const void* in, int64_t ld_in, float* out, int64_t ld_out, int rows, int cols, hipStream_t s, int f16_terms) {
   const int64_t total = (int64_t)rows * cols;
   if (total <= 0) return;
   const int grid = (int)(cdiv64(total, 256) < 8192 ? cdiv64(total, 256) : 8192);
-  hipLaunchKernelGGL(unsplit_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const sp16*>(in), ld_in, out, ld_out, rows,
-                     cols);
+  if (f16_terms)
+    hipLaunchKernelGGL(unsplit_kernel<sp16h>, dim3(grid), dim3(256), 0, s, reinterpret_cast<const sp16h*>(in), ld_in, out, ld_out,
+                       rows, cols);
+  else
+    hipLaunchKernelGGL(unsplit_kernel<sp16>, dim3(grid), dim3(256), 0, s, reinterpret_cast<const sp16*>(in), ld_in, out, ld_out, rows,
+                       cols);
 }
 
 template <typename T>
@@ -633,6 +642,7 @@ template void launch_im2col_conv1<float>(const float*, int, int, int, int, int, 
 template void launch_im2col_conv1<bf16>(const float*, int, int, int, int, int, void*, hipStream_t);
 template void launch_im2col_conv1<f16>(const float*, int, int, int, int, int, void*, hipStream_t);
 template void launch_im2col_conv1<sp16>(const float*, int, int, int, int, int, void*, hipStream_t);
+template void launch_im2col_conv1<sp16h>(const float*, int, int, int, int, int, void*, hipStream_t);
 
 // f-4: ImageBind audio head tail (imagebind_model.py:425-428): y = x / max(||x||_2, 1e-12) * scale, one block per row
 __global__ __launch_bounds__(256) void l2norm_scale_kernel(const float* __restrict__ x, int D, float scale,

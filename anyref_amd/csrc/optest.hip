@@ -27,6 +27,7 @@ static thread_local std::string g_op_err;
 namespace {
 // t = 3 (split pairs, ANYREF_MODE_PARITY16): the entry points keep their f32 interface -- an f32 operand that the mode
 // carries as a bf16 pair is split into a temporary here, a pair-typed result is read back as hi + lo
+// t = 4 (ANYREF_MODE_PARITY16_F16): the same with f16 pairs and f16 weights
 struct TmpBuf {
   void* p = nullptr;
   explicit TmpBuf(size_t bytes) { HIP_TRY(hipMalloc(&p, bytes ? bytes : 16)); HIP_TRY(hipMemset(p, 0, bytes ? bytes : 16)); }
@@ -46,14 +47,17 @@ int anyref_op_gemm(int t, void* stream, const void* A, const void* W, const floa
     a.A = A; a.lda = K; a.W = W; a.ldw = K; a.bias = bias; a.C = C; a.ldc = N; a.resid = resid; a.ldr = N;
     a.row_map = row_map; a.M = M; a.N = N; a.K = K; a.act = act; a.c_f32 = c_f32;
     if (const char* e = getenv("ANYREF_OPTEST_LDW_PAD")) a.ldw = K + atoi(e);  // probe: padded weight rows
-    if (t == 3) {  // A f32 [M,K] -> pairs; W bf16 [N,K] (K % 64 == 0); C f32 [*, N] either way (read back from pairs if !c_f32)
+    if (t == 3 || t == 4) {  // A f32 [M,K] -> pairs; W bf16 / f16 [N,K] (K % 64 == 0); C f32 [*, N] either way (read back from pairs if !c_f32)
       hipStream_t st = (hipStream_t)stream;
-      if (K % 64) throw std::runtime_error("op_gemm t=3: K % 64 != 0");
+      const bool h16 = t == 4;
+      if (K % 64) throw std::runtime_error("op_gemm t=3/4: K % 64 != 0");
       TmpBuf As((size_t)M * K * 4);
-      launch_convert<sp16>(reinterpret_cast<const float*>(A), K, As.p, K, M, K, st);
+      if (h16) launch_convert<sp16h>(reinterpret_cast<const float*>(A), K, As.p, K, M, K, st);
+      else launch_convert<sp16>(reinterpret_cast<const float*>(A), K, As.p, K, M, K, st);
       a.A = As.p;
       if (c_f32) {
-        launch_gemm<sp16>(a, st);
+        if (h16) launch_gemm<sp16h>(a, st);
+        else launch_gemm<sp16>(a, st);
       } else {
         int rows = M;
         if (row_map) {
@@ -63,8 +67,9 @@ int anyref_op_gemm(int t, void* stream, const void* A, const void* W, const floa
         }
         TmpBuf Cs((size_t)rows * pad64(N) * 4);
         a.C = Cs.p; a.ldc = pad64(N);
-        launch_gemm<sp16>(a, st);
-        launch_unsplit(Cs.p, pad64(N), reinterpret_cast<float*>(C), N, rows, N, st);
+        if (h16) launch_gemm<sp16h>(a, st);
+        else launch_gemm<sp16>(a, st);
+        launch_unsplit(Cs.p, pad64(N), reinterpret_cast<float*>(C), N, rows, N, st, h16);
       }
     }
     else if (t == 0) launch_gemm<float>(a, (hipStream_t)stream);
@@ -81,6 +86,7 @@ int anyref_op_gemv(int t, void* stream, const float* x, const float* gain, float
     a.ldy = N; a.B = B; a.N = N; a.K = K; a.act = act;
     if (const char* e = getenv("ANYREF_OPTEST_LDW_PAD")) a.ldw = K + atoi(e);  // probe: padded weight rows
     if (t == 3) launch_gemv<sp16>(a, (hipStream_t)stream);  // W bf16, x f32 staged as f32
+    else if (t == 4) launch_gemv<sp16h>(a, (hipStream_t)stream);  // W f16
     else if (t == 0) launch_gemv<float>(a, (hipStream_t)stream);
     else if (t == 2) launch_gemv<f16>(a, (hipStream_t)stream);
     else launch_gemv<bf16>(a, (hipStream_t)stream);
@@ -98,7 +104,29 @@ int anyref_op_gemv_xn(int t, void* stream, const float* x, const float* gain, fl
     if (t == 0) launch_gemv<float>(a, (hipStream_t)stream);
     else if (t == 1) launch_gemv<bf16>(a, (hipStream_t)stream);
     else if (t == 2) launch_gemv<f16>(a, (hipStream_t)stream);
-    else throw std::runtime_error("op_gemv_xn: t = 0 / 1 / 2");
+    else if (t == 3) launch_gemv<sp16>(a, (hipStream_t)stream);
+    else if (t == 4) launch_gemv<sp16h>(a, (hipStream_t)stream);
+    else throw std::runtime_error("op_gemv_xn: t = 0 .. 4");
+  });
+}
+
+int anyref_op_split_roundtrip(int t, void* stream, const float* in, float* out, void* hi_out, int rows, int cols) {
+  OP_GUARD({
+    if (t != 3 && t != 4) throw std::runtime_error("op_split_roundtrip: t = 3 / 4");
+    hipStream_t st = (hipStream_t)stream;
+    TmpBuf Ps((size_t)rows * pad64(cols) * 4);
+    if (t == 4) launch_convert<sp16h>(in, cols, Ps.p, pad64(cols), rows, cols, st);
+    else launch_convert<sp16>(in, cols, Ps.p, pad64(cols), rows, cols, st);
+    launch_unsplit(Ps.p, pad64(cols), out, cols, rows, cols, st, t == 4);
+    if (hi_out) {  // the hi term alone: widen the 16-bit words at sp_col(c) on the host side of the test
+      std::vector<uint16_t> h((size_t)rows * pad64(cols) * 2);
+      HIP_TRY(hipStreamSynchronize(st));
+      HIP_TRY(hipMemcpy(h.data(), Ps.p, h.size() * 2, hipMemcpyDeviceToHost));
+      std::vector<uint16_t> hi((size_t)rows * cols);
+      for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < cols; ++c) hi[(size_t)r * cols + c] = h[(size_t)r * pad64(cols) * 2 + sp_col(c)];
+      HIP_TRY(hipMemcpy(hi_out, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
+    }
   });
 }
 
@@ -165,11 +193,12 @@ int anyref_op_norm(int t, void* stream, const float* x, const float* gain, const
     NormArgs a;
     a.x = x; a.ldx = D; a.gain = gain; a.bias = bias; a.y = y; a.ldy = D; a.M = M; a.D = D; a.eps = eps;
     a.rms = rms; a.y_f32 = 1;
-    if (t == 3) {  // the norm writes pairs; y gets hi + lo
+    if (t == 3 || t == 4) {  // the norm writes pairs; y gets hi + lo
       TmpBuf Ys((size_t)M * pad64(D) * 4);
       a.y = Ys.p; a.ldy = pad64(D); a.y_f32 = 0;
-      launch_norm<sp16>(a, (hipStream_t)stream);
-      launch_unsplit(Ys.p, pad64(D), y, D, M, D, (hipStream_t)stream);
+      if (t == 4) launch_norm<sp16h>(a, (hipStream_t)stream);
+      else launch_norm<sp16>(a, (hipStream_t)stream);
+      launch_unsplit(Ys.p, pad64(D), y, D, M, D, (hipStream_t)stream, t == 4);
     } else
     if (t == 0) launch_norm<float>(a, (hipStream_t)stream);
     else if (t == 2) launch_norm<f16>(a, (hipStream_t)stream);
@@ -188,12 +217,12 @@ int anyref_op_attention(int t, void* stream, const void* q, const void* k, const
     a.o_bs = (int64_t)Sq * H * hd; a.o_rs = H * hd; a.o_hs = hd;
     a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.hd = hd; a.scale = scale; a.causal = causal; a.kv_len = kv_len;
     a.rel_h = rel_h; a.rel_w = rel_w; a.kh = kh; a.kw = kw;
-    if (t == 3) {  // f32 operands, pair-typed output rows [B*Sq, H*hd] (H*hd % 64 == 0); o gets hi + lo
-      if ((H * hd) % 64) throw std::runtime_error("op_attention t=3: H * hd % 64 != 0");
+    if (t == 3 || t == 4) {  // f32 operands, pair-typed output rows [B*Sq, H*hd] (H*hd % 64 == 0; t = 4: f16 terms); o gets hi + lo
+      if ((H * hd) % 64) throw std::runtime_error("op_attention t=3/4: H * hd % 64 != 0");
       TmpBuf Os((size_t)B * Sq * H * hd * 4);
-      a.O = Os.p; a.o_split = 1; a.sp16 = 1;
+      a.O = Os.p; a.o_split = t == 4 ? 2 : 1; a.sp16 = 1;
       launch_attention<float>(a, (hipStream_t)stream);
-      launch_unsplit(Os.p, H * hd, reinterpret_cast<float*>(o), H * hd, B * Sq, H * hd, (hipStream_t)stream);
+      launch_unsplit(Os.p, H * hd, reinterpret_cast<float*>(o), H * hd, B * Sq, H * hd, (hipStream_t)stream, t == 4);
     } else
     if (t == 0) launch_attention<float>(a, (hipStream_t)stream);
     else if (t == 2) launch_attention<f16>(a, (hipStream_t)stream);
@@ -210,13 +239,13 @@ int anyref_op_attention_tab(int t, void* stream, const void* q, const void* k, c
     a.q_rs = a.k_rs = a.v_rs = a.o_rs = H * hd; a.q_hs = a.k_hs = a.v_hs = a.o_hs = hd;
     a.B = B; a.H = H; a.Sq = S; a.Sk = S; a.hd = hd; a.scale = scale;
     a.rel_tab_h = tab_h; a.rel_tab_w = tab_w; a.rel_tab_ld = tab_ld; a.kh = kh; a.kw = kw;
-    if (t == 3) {  // split-pair attention: f32 operands and f32 tables, pair-typed output rows; o gets hi + lo
-      if ((H * hd) % 64) throw std::runtime_error("op_attention_tab t=3: H * hd % 64 != 0");
-      if (!attention_takes_rel_tables(4, hd, S, S, kh, kw, true)) throw std::runtime_error("op_attention_tab t=3: not a window shape");
+    if (t == 3 || t == 4) {  // split-pair attention: f32 operands and f32 tables, pair-typed output rows; o gets hi + lo
+      if ((H * hd) % 64) throw std::runtime_error("op_attention_tab t=3/4: H * hd % 64 != 0");
+      if (!attention_takes_rel_tables(4, hd, S, S, kh, kw, true)) throw std::runtime_error("op_attention_tab t=3/4: not a window shape");
       TmpBuf Os((size_t)B * S * H * hd * 4);
-      a.O = Os.p; a.o_split = 1; a.sp16 = 1;
+      a.O = Os.p; a.o_split = t == 4 ? 2 : 1; a.sp16 = 1;
       launch_attention<float>(a, (hipStream_t)stream);
-      launch_unsplit(Os.p, H * hd, reinterpret_cast<float*>(o), H * hd, B * S, H * hd, (hipStream_t)stream);
+      launch_unsplit(Os.p, H * hd, reinterpret_cast<float*>(o), H * hd, B * S, H * hd, (hipStream_t)stream, t == 4);
     } else
     if (t == 2) launch_attention<f16>(a, (hipStream_t)stream);
     else launch_attention<bf16>(a, (hipStream_t)stream);
@@ -244,12 +273,12 @@ int anyref_op_attention_relp(int t, void* stream, const void* q, const void* k, 
     a.q_rs = a.k_rs = a.v_rs = a.o_rs = H * hd; a.q_hs = a.k_hs = a.v_hs = a.o_hs = hd;
     a.B = B; a.H = H; a.Sq = S; a.Sk = S; a.hd = hd; a.scale = scale;
     a.rel_p = rel_p; a.rel_ld = rel_ld; a.rel_hs = (int64_t)B * S * rel_ld; a.kh = kh; a.kw = kw;
-    if (t == 3) {  // split-pair attention: f32 operands, pair-typed output rows; o gets hi + lo
-      if ((H * hd) % 64) throw std::runtime_error("op_attention_relp t=3: H * hd % 64 != 0");
+    if (t == 3 || t == 4) {  // split-pair attention: f32 operands, pair-typed output rows; o gets hi + lo
+      if ((H * hd) % 64) throw std::runtime_error("op_attention_relp t=3/4: H * hd % 64 != 0");
       TmpBuf Os((size_t)B * S * H * hd * 4);
-      a.O = Os.p; a.o_split = 1; a.sp16 = 1;
+      a.O = Os.p; a.o_split = t == 4 ? 2 : 1; a.sp16 = 1;
       launch_attention<float>(a, (hipStream_t)stream);
-      launch_unsplit(Os.p, H * hd, reinterpret_cast<float*>(o), H * hd, B * S, H * hd, (hipStream_t)stream);
+      launch_unsplit(Os.p, H * hd, reinterpret_cast<float*>(o), H * hd, B * S, H * hd, (hipStream_t)stream, t == 4);
     } else
     if (t == 0) launch_attention<float>(a, (hipStream_t)stream);
     else if (t == 2) launch_attention<f16>(a, (hipStream_t)stream);

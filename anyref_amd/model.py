@@ -91,7 +91,8 @@ class AnyRefForCausalLM:
         self.imagebind_ckpt = kwargs.pop("imagebind_ckpt", "model/ImageBind/imagebind_huge.pth")
         self.cfg = cfg
         self.mode = {"parity": _lib.MODE_PARITY, "perf": _lib.MODE_PERF, "perf_fp8w": _lib.MODE_PERF_FP8W,
-                     "parity16": _lib.MODE_PARITY16, "perf_f16": _lib.MODE_PERF_F16}[mode]
+                     "parity16": _lib.MODE_PARITY16, "perf_f16": _lib.MODE_PERF_F16,
+                     "parity16_f16": _lib.MODE_PARITY16_F16}[mode]
         self.mode_name = mode
         self.device_index = device
         self.device = torch.device("cuda", device)
@@ -208,7 +209,9 @@ class AnyRefForCausalLM:
         ("perf" = bf16 storage, fp32 accumulate; "parity" = fp32), default perf.  The reference evaluates in fp16
         (`torch_dtype=torch.float16`), so its checkpoints are fp16: `mode="perf_f16"` (f16 storage, fp32 accumulate, same
         bytes and rate as perf) holds such weights bit for bit, where perf rounds them to bf16 (`inexact_weights` counts
-        the elements that changed)."""
+        the elements that changed).  An fp16 checkpoint that has to meet the tolerance bar (identical greedy ids, mask logits
+        within 1e-3 of the fp32 forward on the checkpoint's own values) takes `mode="parity16_f16"`: the same exact f16
+        storage, every GEMM operand f32 carried as a pair of f16 terms; `parity16` would round such weights to bf16."""
         import json
         import os
         from .checkpoint import read_hf_dir, llm_config_from_hf
@@ -331,7 +334,8 @@ class AnyRefForCausalLM:
     @property
     def inexact_weights(self) -> int:
         """Weight elements the handle holds in a value other than the one it was given (anyref_inexact_weights): 0 in
-        "parity", 0 in "perf_f16" for an fp16 checkpoint, most elements of that checkpoint in "perf" (bf16 storage)."""
+        "parity", 0 in "perf_f16" / "parity16_f16" for an fp16 checkpoint, most elements of that checkpoint in "perf" / "parity16"
+        (bf16 storage)."""
         n = C.c_int64(0)
         self._check(self.lib.anyref_inexact_weights(self.h, C.byref(n)), "inexact_weights")
         return int(n.value)

@@ -52,6 +52,17 @@ extern "C" {
  * evaluation dtype) bit for bit; f16 activations saturate past 65504 as in the reference's fp16 run.  finalize fails, naming
  * the tensor, if a weight lies outside the f16 range.  fp8 weights are not offered with it. */
 #define ANYREF_MODE_PERF_F16 4
+/* PARITY16 with f16 in place of bf16 wherever a weight is stored or multiplied: the tolerance-meeting mode for fp16 checkpoints
+ * (the reference's own evaluation dtype).  LLaMA / CLIP / audio / SAM-encoder weights are stored as f16 exactly as handed over
+ * (anyref_inexact_weights = 0 for ANYREF_F16 input; f32 / bf16 input is rounded to f16 and counted; finalize fails, naming the
+ * tensor, if a weight lies outside +-65504).  Every activation that feeds a matrix product is f32 carried as a PAIR of f16 terms
+ * (hi = f16(a), lo = f16(a - hi): |a - hi - lo| <= max(2^-22 |a|, 2^-25)), one f16 MFMA pass per term into the same f32
+ * accumulator (f16 x f16 is exact there); the decode GEMV multiplies the f32 activation row with the f16 weights.  Attention
+ * products (q, k, v, the KV cache, rel-pos tables: f32 with no stored 16-bit factor) are multiplied as bf16 pairs exactly as in
+ * PARITY16; residual streams, norms and the mask decoder are f32.  Range: a GEMM A-operand (norm / attention output, GELU /
+ * SwiGLU hidden row, image patch) past +-65504 becomes inf in its hi term and shows as NaN outputs; the reference's fp16 run
+ * has the same limit on more tensors. */
+#define ANYREF_MODE_PARITY16_F16 5
 
 typedef struct anyref_config {
   int32_t abi_version; /* = ANYREF_ABI_VERSION */

@@ -5,7 +5,8 @@
  * `t` selects the storage type: 0 = f32 (MFMA 16x16x4 f32), 1 = bf16 (MFMA 16x16x32 bf16), 3 = split pairs (ANYREF_MODE_PARITY16: f32
  * operands at the interface, carried as two bf16 terms inside; weights bf16; gemm / gemv / norm / attention entries), 2 = f16 (MFMA 16x16x32
  * f16: the SAM image encoder of the perf build and every tower of ANYREF_MODE_PERF_F16; GEMM, GEMV, norm, attention, decode
- * attention and RoPE entries).
+ * attention and RoPE entries), 4 = split pairs with f16 terms (ANYREF_MODE_PARITY16_F16: as 3 with f16 weights; the attention
+ * entries multiply as 3 does and write their output rows as f16 pairs).
  * All pointers are device pointers; `stream` is a hipStream_t.
  */
 #ifndef ANYREF_HIP_OPS_H
@@ -21,11 +22,14 @@ int anyref_op_gemm(int t, void* stream, const void* A, const void* W, const floa
 /* y = act(rmsnorm?(x) W^T) [* (x W2^T)] + resid;  x,y f32; W in type t */
 int anyref_op_gemv(int t, void* stream, const float* x, const float* gain, float eps, const void* W,
                    const void* W2, const float* bias, float* y, const float* resid, int B, int N, int K, int act);
-/* anyref_op_gemv (t = 0 / 1 / 2) plus the f32 copy of the RMS-normalised rows the lm_head GEMV writes (needs gain):
+/* anyref_op_gemv (t = 0 .. 4) plus the f32 copy of the RMS-normalised rows the lm_head GEMV writes (needs gain):
  * xn_out[(xn_row_map ? xn_row_map[b] : b) * xn_ld + k], xn_out 16-byte aligned, xn_ld % 4 == 0 */
 int anyref_op_gemv_xn(int t, void* stream, const float* x, const float* gain, float eps, const void* W, const void* W2,
                       const float* bias, float* y, const float* resid, int B, int N, int K, int act, float* xn_out,
                       const int32_t* xn_row_map, int xn_ld);
+/* f32 [rows, cols] -> pair-typed rows (t = 3: bf16 terms, t = 4: f16 terms; launch_convert) -> out f32 = hi + lo
+ * (launch_unsplit); hi_out (optional, device, rows * cols 16-bit words): the raw hi terms */
+int anyref_op_split_roundtrip(int t, void* stream, const float* in, float* out, void* hi_out, int rows, int cols);
 /* the model's RoPE table: out_host f32 [S][2][hd/2] = cos | sin of pos * theta^(-2d/hd) (HOST pointer) */
 int anyref_op_rope_table(int S, int hd, float theta, float* out_host);
 /* the decode step's attention as the model runs it (t = 0 f32 / 1 bf16 / 2 f16 cache): qkv f32 [B, 3*H*hd], pos i32 [B], cs_tab

@@ -9,7 +9,10 @@ per handle gives the per-tag averages of the decode GEMVs and the decode attenti
   {"ms_per_image": {mode: {median, min, max, rounds: [...]}}, "device_bytes": {mode: n}, "inexact_weights": {mode: n},
    "tags": {mode: {tag: us per launch}}, "f16_over_bf16": {median image ratio, per GEMV tag pair ratio}}
 
-usage: python tools/ab_perf_f16.py [--rounds 5] [--steps 20] [--warmup 3]
+`--modes A,B` alternates any two modes the same way (B over A), e.g. `--modes parity16,parity16_f16`: the ratio keys are then
+named "<B>_over_<A>" and the GEMV tags are paired through the modes' type tokens (sp16 / sp16h / bf16 / f16 / f32).
+
+usage: python tools/ab_perf_f16.py [--rounds 5] [--steps 20] [--warmup 3] [--modes perf,perf_f16]
 """
 import argparse
 import json
@@ -28,15 +31,22 @@ from anyref_amd.model import AnyRefForCausalLM  # noqa: E402
 from anyref_amd.synth import synth_state_dict  # noqa: E402
 
 MODES = ("perf", "perf_f16")
+TOKEN = {"parity": "f32", "perf": "bf16", "perf_fp8w": "fp8w", "perf_f16": "f16", "parity16": "sp16", "parity16_f16": "sp16h"}
 T_NEW = 10
 
 
 def main():
+    global MODES
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20, help="generate calls per handle and round")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--modes", default=",".join(MODES), help="two mode names, A,B: B is reported over A")
     args = ap.parse_args()
+    MODES = tuple(args.modes.split(","))
+    if len(MODES) != 2 or any(m not in TOKEN for m in MODES):
+        raise SystemExit("ab_perf_f16: --modes takes two of " + ", ".join(TOKEN))
+    A, B = MODES
     if not torch.cuda.is_available():
         raise SystemExit("ab_perf_f16: needs an MI355X (there is no CPU measurement)")
     dev = torch.device("cuda", 0)
@@ -87,10 +97,10 @@ def main():
         tags[mode] = {k: round(v["ms"] * 1e3 / max(1, v["count"]), 2) for k, v in sorted(prof.items())
                       if k.startswith(("gemv_", "decode_attn_"))}
     ratio_tags = {}
-    for k, v in tags["perf_f16"].items():
-        kb = k.replace("_f16", "_bf16")
-        if kb in tags["perf"] and tags["perf"][kb] > 0:
-            ratio_tags[f"{k}/{kb}"] = round(v / tags["perf"][kb], 4)
+    for k, v in tags[B].items():
+        kb = k.replace("_" + TOKEN[B], "_" + TOKEN[A])
+        if kb in tags[A] and tags[A][kb] > 0:
+            ratio_tags[f"{k}/{kb}"] = round(v / tags[A][kb], 4)
     med = {mode: statistics.median(per[mode]) for mode in MODES}
     out = dict(
         workload="c2 (7B + ViT-L + SAM-H 1024^2, S 320, 10 new tokens), f16-rounded N(0, 0.02^2) weights, batch 1",
@@ -100,7 +110,7 @@ def main():
         device_bytes={mode: models[mode].device_bytes for mode in MODES},
         inexact_weights={mode: models[mode].inexact_weights for mode in MODES},
         tags_us=tags,
-        f16_over_bf16=dict(image=round(med["perf_f16"] / med["perf"], 4), tags=ratio_tags))
+        **{("f16_over_bf16" if MODES == ("perf", "perf_f16") else f"{B}_over_{A}"): dict(image=round(med[B] / med[A], 4), tags=ratio_tags)})
     print(json.dumps(out), flush=True)
 
 

@@ -7,6 +7,8 @@
   * the LDS-DMA GEMM must not wait vmcnt(0) in front of a tile's first ds_read (Makefile note on gemm.o)
   * the f16 decode GEMV (ANYREF_MODE_PERF_F16) must multiply on the packed f16 dot (v_dot2[c]_f32_f16), not fall back to
     unpack + FMA
+  * the f16-pair GEMM (ANYREF_MODE_PARITY16_F16) must multiply on the f16 MFMA only (a bf16 MFMA there would read f16 terms as
+    bf16 words), and its decode GEMV must exist
 
 usage: python tools/check_isa.py    (compiles anyref_amd/csrc/*.hip to assembly under /tmp)
 """
@@ -28,13 +30,13 @@ def asm_of(src, strict):
 def main():
     bad = 0
     allowed_scratch = ()
-    for src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemv.hip", "attention.hip", "ops.hip"):
-        s = asm_of(src, strict=src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemv.hip"))
+    for src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemm_sp16h.hip", "gemv.hip", "attention.hip", "ops.hip"):
+        s = asm_of(src, strict=src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemm_sp16h.hip", "gemv.hip"))
         for name, seg in re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", s):
             if int(seg) > 0 and not any(a in name for a in allowed_scratch):
                 print(f"FAIL {src}: {name} uses {seg} bytes of scratch")
                 bad += 1
-        if src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip"):
+        if src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemm_sp16h.hip"):
             for m in re.finditer(r"^(_ZN6anyref16gemm_glds_kernel\S*):\n(.*?)\.Lfunc_end", s, re.S | re.M):
                 lines = m.group(2).split("\n")
                 n = sum(1 for k, l in enumerate(lines)
@@ -42,7 +44,19 @@ def main():
                 if n:
                     print(f"FAIL {src}: {m.group(1)} waits vmcnt(0) before {n} ds_read group(s)")
                     bad += 1
+        if src == "gemm_sp16h.hip":
+            kernels = re.findall(r"^(_ZN6anyref16gemm_glds_kernel\S*):\n(.*?)\.Lfunc_end", s, re.S | re.M)
+            if not kernels:
+                print("FAIL gemm_sp16h.hip: no LDS-DMA GEMM instantiation found")
+                bad += 1
+            for name, body in kernels:
+                if "v_mfma_f32_16x16x32_f16" not in body or re.search(r"v_mfma_f32_16x16x\d+_bf16", body):
+                    print(f"FAIL gemm_sp16h.hip: {name} does not multiply on the f16 MFMA alone")
+                    bad += 1
         if src == "gemv.hip":
+            if not re.search(r"^_ZN6anyref11gemv_kernelINS_5sp16hE\S*:", s, re.M):
+                print("FAIL gemv.hip: no f16-pair decode GEMV instantiation found")
+                bad += 1
             f16 = re.findall(r"^(_ZN6anyref11gemv_kernelINS_3f16E\S*):[^\n]*\n(.*?)\.Lfunc_end", s, re.S | re.M)
             if not f16:
                 print("FAIL gemv.hip: no f16 decode GEMV instantiation found")
