@@ -47,6 +47,35 @@ _I = C.c_int
 _F = C.c_float
 _L = C.c_int64
 
+
+class GemmEx(C.Structure):
+    """anyref_gemm_ex (include/anyref_hip_ops.h)"""
+    _fields_ = ([(n, _P) for n in ("A", "W", "bias", "C", "resid", "row_map", "a_row_map", "norm_gain", "norm_bias",
+                                   "norm_out", "slabs_out")] +
+                [(n, _L) for n in ("sA", "sW", "sC", "sR", "sBias")] +
+                [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldw", "ldc", "ldr", "norm_ld", "act", "c_f32",
+                                          "swiglu_pairs", "slabs", "max_wg", "batch")] +
+                [("alpha", _F), ("norm_eps", _F), ("norm_done", C.c_int32)])
+
+
+class NormEx(C.Structure):
+    """anyref_norm_ex"""
+    _fields_ = ([(n, _P) for n in ("x", "gain", "bias", "y", "row_map", "fill_dst", "fill_rows", "fill_bias")] +
+                [(n, C.c_int32) for n in ("M", "D", "ldx", "ldy", "rms", "y_f32", "act", "fill_ld", "fill_n", "fill_N",
+                                          "fill_fallback")] +
+                [("eps", _F), ("fill_done", C.c_int32)])
+
+
+class AttnEx(C.Structure):
+    """anyref_attn_ex"""
+    _fields_ = ([(n, _P) for n in ("q", "k", "v", "o", "q_pos0", "kv_len", "q_len", "rel_h", "rel_w", "rel_p",
+                                   "rel_tab_h", "rel_tab_w")] +
+                [(n, _L) for n in ("q_bs", "q_rs", "q_hs", "k_bs", "k_rs", "k_hs", "v_bs", "v_rs", "v_hs", "o_bs", "o_rs",
+                                   "o_hs", "rel_hs")] +
+                [(n, C.c_int32) for n in ("B", "H", "Sq", "Sk", "hd", "causal", "kh", "kw", "rel_ld", "rel_tab_ld",
+                                          "max_wg")] +
+                [("scale", _F)])
+
 # name -> (restype, argtypes): every symbol the two headers declare
 SYMBOLS = {
     "anyref_create": (_I, [C.POINTER(AnyrefConfig), _I, C.POINTER(_P)]),
@@ -113,6 +142,10 @@ SYMBOLS = {
     "anyref_op_rel_pos": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "anyref_op_postprocess": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "anyref_op_last_error": (C.c_char_p, []),
+    "anyref_op_gemm_ex": (_I, [_I, _P, C.POINTER(GemmEx)]),
+    "anyref_op_norm_ex": (_I, [_I, _P, C.POINTER(NormEx)]),
+    "anyref_op_attention_ex": (_I, [_I, _P, C.POINTER(AttnEx)]),
+    "anyref_op_last_tags": (C.c_char_p, []),
 }
 
 _lib = None

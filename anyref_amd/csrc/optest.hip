@@ -9,10 +9,11 @@
 using namespace anyref;
 
 static thread_local std::string g_op_err;
+static thread_local std::string g_op_tags;
 
-#define OP_GUARD(body)                                   \
+#define OP_GUARD(...)                                    \
   try {                                                  \
-    body;                                                \
+    __VA_ARGS__;                                         \
     hipError_t _e = hipGetLastError();                   \
     if (_e != hipSuccess) {                              \
       g_op_err = std::string("HIP error: ") + hipGetErrorString(_e); \
@@ -34,11 +35,151 @@ struct TmpBuf {
   ~TmpBuf() { (void)hipDeviceSynchronize(); (void)hipFree(p); }
 };
 inline int pad64(int k) { return (k + 63) / 64 * 64; }
+// books the launch tags of one *_ex call: a Profiler on g_prof for the duration of the call
+struct TagScope {
+  Profiler prof;
+  Profiler* prev;
+  hipStream_t st;
+  explicit TagScope(hipStream_t s) : prev(g_prof), st(s) {
+    g_op_tags.clear();
+    prof.on = true;
+    g_prof = &prof;
+  }
+  ~TagScope() {
+    g_prof = prev;
+    (void)hipStreamSynchronize(st);  // the bracket events are destroyed with the Profiler
+    for (auto& kv : prof.stats()) g_op_tags += (g_op_tags.empty() ? "" : ",") + kv.first;
+  }
+};
+template <typename F>
+void by_type(int t, F&& f) {  // f(T()) for the storage type t = 0 .. 4
+  if (t == 0) f(float());
+  else if (t == 1) f(bf16());
+  else if (t == 2) f(f16());
+  else if (t == 3) f(sp16());
+  else if (t == 4) f(sp16h());
+  else throw std::runtime_error("op: t = 0 .. 4");
+}
 }  // namespace
 
 extern "C" {
 
 const char* anyref_op_last_error(void) { return g_op_err.c_str(); }
+const char* anyref_op_last_tags(void) { return g_op_tags.c_str(); }
+
+int anyref_op_gemm_ex(int t, void* stream, anyref_gemm_ex* e) {
+  OP_GUARD({
+    hipStream_t st = (hipStream_t)stream;
+    e->norm_done = 0;
+    bool fused = false;
+    GemmArgs a;
+    a.A = e->A; a.W = e->W; a.bias = e->bias; a.C = e->C; a.resid = e->resid; a.row_map = e->row_map;
+    a.a_row_map = e->a_row_map; a.M = e->M; a.N = e->N; a.K = e->K; a.lda = e->lda; a.ldw = e->ldw; a.ldc = e->ldc;
+    a.ldr = e->ldr; a.act = e->act; a.c_f32 = e->c_f32; a.alpha = e->alpha; a.swiglu_pairs = e->swiglu_pairs;
+    a.max_wg = e->max_wg; a.norm_gain = e->norm_gain; a.norm_out = e->norm_out; a.norm_ld = e->norm_ld;
+    a.norm_eps = e->norm_eps; a.norm_bias = e->norm_bias; a.slabs_out = e->slabs_out; a.slabs = e->slabs;
+    a.norm_done = &fused; a.batch = e->batch; a.sA = e->sA; a.sW = e->sW; a.sC = e->sC; a.sR = e->sR; a.sBias = e->sBias;
+    TagScope tags(st);
+    if (t == 3 || t == 4) {  // A f32 -> pairs; a pair-typed C / norm_out is read back as hi + lo into the f32 array given
+      const bool h16 = t == 4;
+      if (e->batch != 1 || e->a_row_map || e->row_map || e->K % 64)
+        throw std::runtime_error("op_gemm_ex t=3/4: batch 1, no row maps, K % 64 == 0");
+      const int nc = e->swiglu_pairs ? e->N / 2 : e->N;
+      TmpBuf As((size_t)e->M * e->K * 4), Cs(e->c_f32 ? 0 : (size_t)e->M * pad64(nc) * 4),
+          Ns(e->norm_out ? (size_t)e->M * pad64(e->N) * 4 : 0);
+      if (h16) launch_convert<sp16h>(reinterpret_cast<const float*>(e->A), e->lda, As.p, e->K, e->M, e->K, st);
+      else launch_convert<sp16>(reinterpret_cast<const float*>(e->A), e->lda, As.p, e->K, e->M, e->K, st);
+      a.A = As.p; a.lda = e->K;
+      if (!e->c_f32 && !e->slabs_out) { a.C = Cs.p; a.ldc = pad64(nc); }
+      if (e->norm_out) { a.norm_out = Ns.p; a.norm_ld = pad64(e->N); }
+      if (h16) launch_gemm<sp16h>(a, st);
+      else launch_gemm<sp16>(a, st);
+      if (!e->c_f32 && !e->slabs_out) launch_unsplit(Cs.p, pad64(nc), reinterpret_cast<float*>(e->C), e->ldc, e->M, nc, st, h16);
+      if (e->norm_out && fused)
+        launch_unsplit(Ns.p, pad64(e->N), reinterpret_cast<float*>(e->norm_out), e->norm_ld, e->M, e->N, st, h16);
+    } else {
+      by_type(t, [&](auto T0) {
+        using T = decltype(T0);
+        if constexpr (!is_split<T>::value) launch_gemm<T>(a, st);
+      });
+    }
+    e->norm_done = fused ? 1 : 0;
+  });
+}
+
+int anyref_op_norm_ex(int t, void* stream, anyref_norm_ex* e) {
+  OP_GUARD({
+    hipStream_t st = (hipStream_t)stream;
+    e->fill_done = 0;
+    bool filled = false;
+    NormArgs a;
+    a.x = e->x; a.ldx = e->ldx; a.gain = e->gain; a.bias = e->bias; a.y = e->y; a.ldy = e->ldy; a.row_map = e->row_map;
+    a.M = e->M; a.D = e->D; a.eps = e->eps; a.rms = e->rms; a.y_f32 = e->y_f32; a.act = e->act;
+    a.fill_dst = e->fill_dst; a.fill_ld = e->fill_ld; a.fill_n = e->fill_n; a.fill_N = e->fill_N;
+    a.fill_rows = e->fill_rows; a.fill_bias = e->fill_bias; a.fill_done = &filled;
+    TagScope tags(st);
+    if (t == 3 || t == 4) {  // the norm writes pairs: y's rows go through a pair-typed temporary and come back as hi + lo
+      const bool h16 = t == 4;
+      if (e->y_f32) throw std::runtime_error("op_norm_ex t=3/4: the pair-typed output only");
+      int rows = e->M;
+      if (e->row_map) {
+        std::vector<int> h(e->M);
+        HIP_TRY(hipMemcpy(h.data(), e->row_map, (size_t)e->M * 4, hipMemcpyDeviceToHost));
+        for (int v : h) rows = std::max(rows, v + 1);
+      }
+      const int ld = pad64(e->D);
+      TmpBuf Ys((size_t)rows * ld * 4);
+      // (rows the map drops keep what y held: carried through the temporary)
+      if (h16) launch_convert<sp16h>(reinterpret_cast<const float*>(e->y), e->ldy, Ys.p, ld, rows, e->D, st);
+      else launch_convert<sp16>(reinterpret_cast<const float*>(e->y), e->ldy, Ys.p, ld, rows, e->D, st);
+      a.y = Ys.p; a.ldy = ld;
+      if (h16) launch_norm<sp16h>(a, st);
+      else launch_norm<sp16>(a, st);
+      launch_unsplit(Ys.p, ld, reinterpret_cast<float*>(e->y), e->ldy, rows, e->D, st, h16);
+      if (!filled && e->fill_fallback && e->fill_n > 0)
+        launch_fill_rows_bias<float>(e->fill_dst, e->fill_ld, e->fill_rows, e->fill_n, e->fill_bias, e->fill_N, st);
+    } else {
+      by_type(t, [&](auto T0) {
+        using T = decltype(T0);
+        if constexpr (!is_split<T>::value) {
+          launch_norm<T>(a, st);
+          if (!filled && e->fill_fallback && e->fill_n > 0)
+            launch_fill_rows_bias<T>(e->fill_dst, e->fill_ld, e->fill_rows, e->fill_n, e->fill_bias, e->fill_N, st);
+        }
+      });
+    }
+    e->fill_done = filled ? 1 : 0;
+  });
+}
+
+int anyref_op_attention_ex(int t, void* stream, anyref_attn_ex* e) {
+  OP_GUARD({
+    hipStream_t st = (hipStream_t)stream;
+    AttnArgs a;
+    a.Q = e->q; a.K = e->k; a.V = e->v; a.O = e->o;
+    a.q_bs = e->q_bs; a.q_rs = e->q_rs; a.q_hs = e->q_hs; a.k_bs = e->k_bs; a.k_rs = e->k_rs; a.k_hs = e->k_hs;
+    a.v_bs = e->v_bs; a.v_rs = e->v_rs; a.v_hs = e->v_hs; a.o_bs = e->o_bs; a.o_rs = e->o_rs; a.o_hs = e->o_hs;
+    a.B = e->B; a.H = e->H; a.Sq = e->Sq; a.Sk = e->Sk; a.hd = e->hd; a.scale = e->scale; a.causal = e->causal;
+    a.q_pos0 = e->q_pos0; a.kv_len = e->kv_len; a.q_len = e->q_len; a.rel_h = e->rel_h; a.rel_w = e->rel_w;
+    a.kh = e->kh; a.kw = e->kw; a.rel_p = e->rel_p; a.rel_hs = e->rel_hs; a.rel_ld = e->rel_ld;
+    a.rel_tab_h = e->rel_tab_h; a.rel_tab_w = e->rel_tab_w; a.rel_tab_ld = e->rel_tab_ld; a.max_wg = e->max_wg;
+    TagScope tags(st);
+    if (t == 3) {  // split-pair attention: f32 operands, pair-typed output rows; o gets hi + lo
+      if (e->o_rs % 64 || e->o_bs != (int64_t)e->Sq * e->o_rs || e->H * e->hd > e->o_rs)
+        throw std::runtime_error("op_attention_ex t=3: o rows are whole pair rows (o_rs % 64 == 0, o_bs == Sq * o_rs)");
+      const int rows = e->B * e->Sq, cols = e->H * e->hd;
+      TmpBuf Os((size_t)rows * e->o_rs * 4);
+      // (rows past q_len keep what o held: carried through the temporary)
+      launch_convert<sp16>(reinterpret_cast<const float*>(e->o), e->o_rs, Os.p, e->o_rs, rows, cols, st);
+      a.O = Os.p; a.o_split = 1; a.sp16 = 1;
+      launch_attention<float>(a, st);
+      launch_unsplit(Os.p, e->o_rs, reinterpret_cast<float*>(e->o), e->o_rs, rows, cols, st, 0);
+    } else if (t == 0) launch_attention<float>(a, st);
+    else if (t == 2) launch_attention<f16>(a, st);
+    else if (t == 1) launch_attention<bf16>(a, st);
+    else throw std::runtime_error("op_attention_ex: t = 0 .. 3");
+  });
+}
 
 int anyref_op_gemm(int t, void* stream, const void* A, const void* W, const float* bias, void* C,
                    const float* resid, const int32_t* row_map, int M, int N, int K, int act, int c_f32) {

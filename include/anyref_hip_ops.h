@@ -137,6 +137,60 @@ int anyref_op_postprocess(void* stream, const float* low, int n, int lh, int lw,
                           int W, float* out);
 const char* anyref_op_last_error(void);
 
+/* ---- the launch forms the model itself uses (tests/test_gpu_gemm_forms.py): one plain struct per launcher, mirroring the
+ * fields of GemmArgs / NormArgs / AttnArgs (anyref_amd/csrc/kernels.h) a test needs.  Pointers are device pointers, strides in
+ * elements.  Every call records the launch tags booked while it ran (anyref_op_last_tags). ---- */
+typedef struct anyref_gemm_ex {
+  const void* A;            /* T [batch][M, K] at row stride lda, batch stride sA (t = 3 / 4: f32, batch 1) */
+  const void* W;            /* T [N, K] at row stride ldw, batch stride sW (t = 3: bf16, t = 4: f16) */
+  const float* bias;        /* [N], batch stride sBias */
+  void* C;                  /* f32 (c_f32) or T (t = 3 / 4: f32 either way, read back from pairs if !c_f32) */
+  const float* resid;       /* f32 at row stride ldr, batch stride sR; may alias C */
+  const int32_t* row_map;
+  const int32_t* a_row_map;
+  const float* norm_gain;
+  const float* norm_bias;   /* set: LayerNorm */
+  void* norm_out;           /* T [M, N] at row stride norm_ld (t = 3 / 4: f32, read back from pairs when the norm was fused) */
+  float* slabs_out;         /* f32 [slabs][M, N] */
+  int64_t sA, sW, sC, sR, sBias;
+  int32_t M, N, K, lda, ldw, ldc, ldr, norm_ld;
+  int32_t act, c_f32, swiglu_pairs, slabs, max_wg, batch;
+  float alpha, norm_eps;
+  int32_t norm_done;        /* out: the norm rode on the split-K reduction */
+} anyref_gemm_ex;
+int anyref_op_gemm_ex(int t, void* stream, anyref_gemm_ex* e);
+
+typedef struct anyref_norm_ex {
+  const float* x;           /* f32 [M, D] at row stride ldx */
+  const float* gain;
+  const float* bias;        /* NULL with rms */
+  void* y;                  /* f32 (y_f32) or T at row stride ldy (t = 3 / 4: f32 holding hi + lo of the pairs) */
+  const int32_t* row_map;   /* destination row, < 0: dropped */
+  void* fill_dst;           /* T (t = 3 / 4: f32) rows at stride fill_ld: fill_dst[fill_rows[i], 0:fill_N) = fill_bias */
+  const int32_t* fill_rows;
+  const float* fill_bias;
+  int32_t M, D, ldx, ldy, rms, y_f32, act;
+  int32_t fill_ld, fill_n, fill_N;
+  int32_t fill_fallback;    /* 1: launch_fill_rows_bias when the norm kernel did not take the side job (as the model does) */
+  float eps;
+  int32_t fill_done;        /* out: the wide-row kernel wrote the fill rows */
+} anyref_norm_ex;
+int anyref_op_norm_ex(int t, void* stream, anyref_norm_ex* e);
+
+typedef struct anyref_attn_ex {
+  const void *q, *k, *v;    /* T (t = 0 .. 3; t = 3: f32) at the batch / row / head strides below */
+  void* o;                  /* T (t = 3: f32 holding hi + lo; o_bs == Sq * o_rs, o_rs % 64 == 0) */
+  const int32_t *q_pos0, *kv_len, *q_len;
+  const float *rel_h, *rel_w, *rel_p;
+  const void *rel_tab_h, *rel_tab_w;
+  int64_t q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs, o_bs, o_rs, o_hs, rel_hs;
+  int32_t B, H, Sq, Sk, hd, causal, kh, kw, rel_ld, rel_tab_ld, max_wg;
+  float scale;
+} anyref_attn_ex;
+int anyref_op_attention_ex(int t, void* stream, anyref_attn_ex* e);
+/* the launch tags (kernels.h ProfScope) booked during the last *_ex call of this thread, comma separated */
+const char* anyref_op_last_tags(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,29 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert declared == set(_lib.SYMBOLS), (declared ^ set(_lib.SYMBOLS))
 
 
+def test_launch_form_entries_are_declared_and_their_structs_match_the_header():
+    """anyref_op_gemm_ex / norm_ex / attention_ex / last_tags: in the header and the ctypes table, and the ctypes structs list
+    the header's fields in the header's order with the header's types"""
+    from anyref_amd import _lib
+    txt = open(os.path.join(ROOT, "include", "anyref_hip_ops.h")).read()
+    for name in ("anyref_op_gemm_ex", "anyref_op_norm_ex", "anyref_op_attention_ex", "anyref_op_last_tags"):
+        assert name in _lib.SYMBOLS and re.search(r"\b%s\s*\(" % name, txt), name
+    ctype = {"int64_t": _lib.C.c_int64, "int32_t": _lib.C.c_int32, "float": _lib.C.c_float}
+    for cname, cls in (("anyref_gemm_ex", _lib.GemmEx), ("anyref_norm_ex", _lib.NormEx), ("anyref_attn_ex", _lib.AttnEx)):
+        body = txt[txt.index("typedef struct %s {" % cname): txt.index("} %s;" % cname)].split("{", 1)[1]
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        fields = []
+        for decl in body.split(";"):
+            decl = decl.strip()
+            if not decl:
+                continue
+            ptr = "*" in decl
+            base = [w for w in decl.replace("*", " ").replace("const", " ").split()][0]
+            for part in decl.replace("const", " ").split(None, 1)[1].split(","):
+                fields.append((part.replace("*", "").strip(), _lib.C.c_void_p if ptr else ctype[base]))
+        assert fields == list(cls._fields_), cname
+
+
 def test_config_struct_matches_header_field_order():
     from anyref_amd import _lib
     txt = open(os.path.join(ROOT, "include", "anyref_hip.h")).read()
