@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(HERE, "libanyref_hip.so")
 ABI_VERSION = 2
 F32, BF16, F16 = 0, 1, 2
 MODE_PARITY, MODE_PERF, MODE_PERF_FP8W, MODE_PARITY16, MODE_PERF_F16, MODE_PARITY16_F16 = 0, 1, 2, 3, 4, 5
+MODE_PERF_INT4W = 6
 
 
 class AnyrefConfig(C.Structure):
@@ -120,6 +121,9 @@ SYMBOLS = {
     "anyref_op_gemm_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "anyref_op_quant_fp8": (_I, [_P, _P, _I, _I, _P, _P]),
     "anyref_op_gemv_fp8": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
+    "anyref_op_quant_int4": (_I, [_P, _P, _I, _I, _P, _P]),
+    "anyref_op_dequant_int4": (_I, [_P, _P, _P, _I, _I, _P]),
+    "anyref_op_gemv_int4": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     "anyref_op_iou_counts": (_I, [_P, _P, _P, _I, _L, _P]),
     "anyref_op_avs_counts": (_I, [_P, _P, _P, _I, _L, _P, _I, _F, _P, _P]),
     "anyref_op_sam_preprocess": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),

@@ -743,6 +743,11 @@ static void gemv_dispatch(const GemvArgs& a_in, int b0, int nb, hipStream_t s) {
 
 template <typename T>
 void launch_gemv(const GemvArgs& a, hipStream_t s) {
+  if (a.w_int4) {  // int4 group-quantised weights: a kernel family of its own (gemv_int4.hip), passes of up to 4 rows
+    if (!std::is_same<T, bf16>::value) throw std::runtime_error("gemv: int4 weights need the bf16 mode");
+    launch_gemv_int4(a, s);
+    return;
+  }
   const int VN = a.w_fp8 ? 16 : Vec16<typename split_term<T>::type>::N;
   if (a.K % VN || ((uintptr_t)a.W & 15)) throw std::runtime_error("gemv: K must be a multiple of 16 bytes");
   if (a.w_fp8 && (!std::is_same<T, bf16>::value || !a.wscale || (a.W2 && !a.wscale2)))

@@ -189,6 +189,12 @@ struct GemvArgs {
   const float* wscale = nullptr;
   const float* wscale2 = nullptr;
   int ws_stride = 1;
+  // int4 group-quantised weights (T = bf16 activations; gemv_int4.hip): W / W2 are nibble rows (ldw in BYTES), gscale / gscale2
+  // bf16 [N, ceil(K / 128)] at row stride ld_gscale (elements); launch_gemv<bf16> hands the call to launch_gemv_int4
+  int w_int4 = 0;
+  const void* gscale = nullptr;
+  const void* gscale2 = nullptr;
+  int ld_gscale = 0;
   // optional f32 copy of the normalised input rows (needs `gain`): xn_out[(xn_row_map ? xn_row_map[b] : b) * xn_ld + k]
   float* xn_out = nullptr;
   const int* xn_row_map = nullptr;
@@ -208,6 +214,16 @@ void launch_quant_fp8_rows(const float* src, int lds, int N, int K, uint8_t* q, 
 // q * scale -> bf16 [N, K] (prefill GEMM operand)
 void launch_dequant_fp8_rows(const uint8_t* q, int ldq, const float* scale, int N, int K, void* out_bf16, int ldo,
                              hipStream_t s);
+// int4 group quantisation (ANYREF_MODE_PERF_INT4W; the format: gemv_int4.hip / anyref_amd/quant.py): src f32 [N, K] (row stride
+// lds) -> nibble rows q (ldq bytes apart: 2 ldq for the gate / up interleave) + bf16 scales [N, ceil(K / 128)] (ld_scale apart)
+// inexact (optional, device): += elements with q * s != W
+void launch_quant_int4_rows(const float* src, int lds, int N, int K, uint8_t* q, int ldq, void* scale_bf16, int ld_scale,
+                            hipStream_t s, unsigned long long* inexact = nullptr);
+// q * s -> bf16 [N, K] (prefill GEMM operand); every element exact by construction
+void launch_dequant_int4_rows(const uint8_t* q, int ldq, const void* scale_bf16, int ld_scale, int N, int K, void* out_bf16,
+                              int ldo, hipStream_t s);
+// the decode GEMV on int4 weights (GemvArgs::w_int4): 1 - 4 batch rows per pass
+void launch_gemv_int4(const GemvArgs& a, hipStream_t s);
 
 // y[dst(m)] = LN(x[m]) * g + b   (rms: y = x * rsqrt(mean x^2 + eps) * g)
 struct NormArgs {

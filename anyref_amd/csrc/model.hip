@@ -144,6 +144,11 @@ struct Lin {  // nn.Linear packed in T
   // fp8 weight-only mode (LLM linears): e4m3 bytes [n, k] + one f32 scale per output row; w stays null
   uint8_t* w8 = nullptr;
   float* ws = nullptr;
+  // int4 weight-only mode (LLM linears without lm_head; gemv_int4.hip): nibble rows [n, ld4 bytes] + one bf16 scale per 128 k
+  // [n, ng4]; w stays null
+  uint8_t* w4 = nullptr;
+  bf16* s4 = nullptr;
+  int ld4 = 0, ng4 = 0;
 };
 struct LinF {  // nn.Linear kept in f32
   float* w = nullptr;
@@ -184,6 +189,8 @@ class Model : public ModelBase {
   Model(const anyref_config& c, int device) : ModelBase(c, device) {
     fp8w_ = c.mode == ANYREF_MODE_PERF_FP8W;
     if (fp8w_ && !std::is_same<T, bf16>::value) throw std::runtime_error("fp8 weights need the bf16 compute mode");
+    int4w_ = c.mode == ANYREF_MODE_PERF_INT4W;
+    if (int4w_ && !std::is_same<T, bf16>::value) throw std::runtime_error("int4 weights need the bf16 compute mode");
     // the split-pair encoder is twice as long as the 16-bit one: spread over 8 decode steps instead of 6
     // (scratch/side_share.py, parity16 at C2: 49.2 - 49.9 ms with 6, 48.3 - 48.6 with 8 - 10; caps other than 128 lose 1 - 10 ms)
     if (SPS && !getenv("ANYREF_SIDE_STEPS")) side_steps_ = 8;
@@ -213,6 +220,7 @@ class Model : public ModelBase {
     if (std::is_same<T, sp16h>::value) return "f32 activations as f16 pairs x f16 weights";
     if (SPT) return "f32 activations as bf16 pairs x bf16 weights";
     if (is_half16<T>::value) return "f16";
+    if (int4w_) return is_half16<TS>::value ? "bf16+int4w, SAM f16" : "bf16+int4w";
     return sizeof(T) == 2 ? (fp8w_ ? (is_half16<TS>::value ? "bf16+fp8w, SAM f16" : "bf16+fp8w")
                                    : (is_half16<TS>::value ? "bf16, SAM f16" : "bf16"))
                           : "f32";
@@ -304,6 +312,12 @@ class Model : public ModelBase {
           a.W = deq_buf_; a.ldw = l.k;
         }
       }
+      if constexpr (std::is_same<T, bf16>::value) {
+        if (l.w4) {  // int4: multiply the (exact) bf16 image of q * s
+          launch_dequant_int4_rows(l.w4, l.ld4, l.s4, l.ng4, l.n, l.k, deq_buf_, l.k, s);
+          a.W = deq_buf_; a.ldw = l.k;
+        }
+      }
     }
     launch_gemm<E>(a, s);
     return fused;
@@ -318,7 +332,13 @@ class Model : public ModelBase {
   void gemv_w(GemvArgs& g, const Lin<W>& l, int row0 = 0) const {
     g.ldw = l.stride();
     g.grid = gemv_grid_;
-    if (l.w8) {
+    if (l.w4) {
+      g.W = l.w4 + (size_t)row0 * l.ld4;
+      g.gscale = l.s4 + (size_t)row0 * l.ng4;
+      g.ldw = l.ld4;
+      g.ld_gscale = l.ng4;
+      g.w_int4 = 1;
+    } else if (l.w8) {
       g.W = l.w8 + (size_t)row0 * l.stride();
       g.wscale = l.ws + row0;
       g.w_fp8 = 1;
@@ -327,7 +347,10 @@ class Model : public ModelBase {
     }
   }
   void gemv_w2(GemvArgs& g, const Lin<W>& l, int row0) const {
-    if (l.w8) {
+    if (l.w4) {
+      g.W2 = l.w4 + (size_t)row0 * l.ld4;
+      g.gscale2 = l.s4 + (size_t)row0 * l.ng4;
+    } else if (l.w8) {
       g.W2 = l.w8 + (size_t)row0 * l.stride();
       g.wscale2 = l.ws + row0;
     } else {
@@ -356,6 +379,27 @@ class Model : public ModelBase {
     l.w8 = reinterpret_cast<uint8_t*>(dalloc((size_t)n * l.ld));
     HIP_TRY(hipMemset(l.w8, 0, (size_t)n * l.ld));
     l.ws = talloc<float>(n);
+    return l;
+  }
+  bool int4w_ = false;
+  // pack rows of a raw f32 tensor as int4 nibbles + group scales into l (rows [row0, row0 + rows)); rstride 2: every second row
+  void pack_rows_int4(Lin<W>& l, int row0, const std::string& name, int rows, int cols, int rstride = 1) {
+    const RawTensor& t = raw(name);
+    if (t.numel() != (int64_t)rows * cols || cols != l.k)
+      throw std::runtime_error("shape mismatch for " + name + " (int4 pack)");
+    launch_quant_int4_rows(t.p, cols, rows, cols, l.w4 + (size_t)row0 * l.ld4, l.ld4 * rstride, l.s4 + (size_t)row0 * l.ng4,
+                           l.ng4 * rstride, 0, weight_counts());
+  }
+  Lin<W> alloc_int4(int n, int k, const std::string& name) {
+    if (k % 16) throw std::runtime_error("int4 weights need K % 16 == 0: " + name + " has K = " + std::to_string(k));
+    Lin<W> l;
+    l.n = n;
+    l.k = k;
+    l.ng4 = cdiv(k, 128);
+    l.ld4 = l.ng4 * 64 + kRowPadBytes;
+    l.w4 = reinterpret_cast<uint8_t*>(dalloc((size_t)n * l.ld4));
+    HIP_TRY(hipMemset(l.w4, 0x88, (size_t)n * l.ld4));  // q = 0
+    l.s4 = talloc<bf16>((size_t)n * l.ng4);
     return l;
   }
   bool skinny_off_ = getenv("ANYREF_NO_SKINNY_GEMV") != nullptr;
@@ -752,7 +796,17 @@ void Model<T, TS>::finalize() {
       L.in_norm = affine(lp + "input_layernorm", false);
       L.post_norm = affine(lp + "post_attention_layernorm", false);
       const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-      if (fp8w_) {
+      if (int4w_) {
+        L.qkv = alloc_int4(3 * H, H, lp + "self_attn.q_proj.weight");
+        for (int j = 0; j < 3; ++j) pack_rows_int4(L.qkv, j * H, lp + "self_attn." + names[j] + ".weight", H, H);
+        L.o = alloc_int4(H, H, lp + "self_attn.o_proj.weight");
+        pack_rows_int4(L.o, 0, lp + "self_attn.o_proj.weight", H, H);
+        L.gu = alloc_int4(2 * F, H, lp + "mlp.gate_proj.weight");  // rows interleaved: 2j = gate_j, 2j + 1 = up_j
+        pack_rows_int4(L.gu, 0, lp + "mlp.gate_proj.weight", F, H, 2);
+        pack_rows_int4(L.gu, 1, lp + "mlp.up_proj.weight", F, H, 2);
+        L.down = alloc_int4(H, F, lp + "mlp.down_proj.weight");
+        pack_rows_int4(L.down, 0, lp + "mlp.down_proj.weight", H, F);
+      } else if (fp8w_) {
         L.qkv = alloc_fp8(3 * H, H);
         for (int j = 0; j < 3; ++j) pack_rows_fp8(L.qkv, j * H, lp + "self_attn." + names[j] + ".weight", H, H);
         L.o = alloc_fp8(H, H);
@@ -803,6 +857,8 @@ void Model<T, TS>::finalize() {
       deq_buf_ = talloc<W>(big);
     } else {
       lm_head_ = pack_linear("lm_head.weight", "", V, H, 8, kRowPadBytes / (int)sizeof(W));
+      // int4: the bf16 image of the largest linear (prefill / teacher / MFMA-decode GEMM operand); lm_head stays bf16
+      if (int4w_) deq_buf_ = talloc<W>(std::max((size_t)2 * F * H, (size_t)3 * H * H));
     }
     // rotary table, same fp32 op order as HF LlamaRotaryEmbedding
     std::vector<float> tab((size_t)S * hd);
@@ -1340,7 +1396,7 @@ void Model<T, TS>::llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev
     Q* vc = vcache_ + cache_layer_stride_ * i;
     if (!h_ready) norm(s, l_x_, H, L.in_norm, l_h_, H, R, H, c.llm_rms_eps, false, true);
     Q* qkeep = (keep_q && i == nl - 1) ? q_last_ : nullptr;
-    if (qkv_slabs_ && !L.qkv.w8 && R > 192 && R <= 320 && H % 128 == 0 && hd % 16 == 0 && !qkv_slabs_off_) {
+    if (qkv_slabs_ && !L.qkv.w8 && !L.qkv.w4 && R > 192 && R <= 320 && H % 128 == 0 && hd % 16 == 0 && !qkv_slabs_off_) {
       // one image's prompt: the projection as two K slices on whole-M tiles (256 workgroups), summed by the RoPE kernel
       GemmArgs a;
       a.A = l_h_; a.lda = H; a.W = L.qkv.w; a.ldw = L.qkv.stride(); a.M = R; a.N = 3 * H; a.K = H;
@@ -1417,7 +1473,7 @@ void Model<T, TS>::llm_decode_step(hipStream_t s, int B, bool keep_q) {
     o.x = d_att_; o.ldx = H; gemv_w(o, L.o); o.y = d_x_; o.resid = d_x_; o.ldy = H; o.B = B; o.N = H; o.K = H;
     launch_gemv<T>(o, s);
     GemvArgs m;
-    m.x = d_x_; m.ldx = H; m.gain = L.post_norm.g; m.eps = c.llm_rms_eps; gemv_w(m, L.gu, 0); gemv_w2(m, L.gu, 1); m.ldw = 2 * L.gu.stride(); m.ws_stride = 2;
+    m.x = d_x_; m.ldx = H; m.gain = L.post_norm.g; m.eps = c.llm_rms_eps; gemv_w(m, L.gu, 0); gemv_w2(m, L.gu, 1); m.ldw = 2 * (L.gu.w4 ? L.gu.ld4 : L.gu.stride()); m.ld_gscale = 2 * L.gu.ng4; m.ws_stride = 2;
     m.y = d_act_; m.ldy = F; m.B = B; m.N = F; m.K = H;
     launch_gemv<T>(m, s);
     GemvArgs d;
@@ -2177,7 +2233,7 @@ void Model<T, TS>::seg_tail(hipStream_t s, const float* sam_images, const int64_
 std::unique_ptr<ModelBase> make_model(const anyref_config& cfg, int device) {
   if (cfg.mode == ANYREF_MODE_PARITY) return std::unique_ptr<ModelBase>(new Model<float>(cfg, device));
   if (cfg.mode == ANYREF_MODE_PARITY16) return std::unique_ptr<ModelBase>(new Model<sp16, sp16>(cfg, device));
-  if (cfg.mode == ANYREF_MODE_PERF || cfg.mode == ANYREF_MODE_PERF_FP8W) {
+  if (cfg.mode == ANYREF_MODE_PERF || cfg.mode == ANYREF_MODE_PERF_FP8W || cfg.mode == ANYREF_MODE_PERF_INT4W) {
     static const bool sam_bf16 = getenv("ANYREF_SAM_BF16") != nullptr;  // A/B: the all-bf16 handle of rounds 1-2
     if (sam_bf16) return std::unique_ptr<ModelBase>(new Model<bf16, bf16>(cfg, device));
     return std::unique_ptr<ModelBase>(new Model<bf16, f16>(cfg, device));

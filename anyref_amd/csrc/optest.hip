@@ -468,6 +468,25 @@ int anyref_op_gemv_fp8(void* stream, const float* x, const float* gain, float ep
   });
 }
 
+int anyref_op_quant_int4(void* stream, const float* src, int N, int K, uint8_t* q, void* scale_bf16) {
+  OP_GUARD(launch_quant_int4_rows(src, K, N, K, q, (K + 127) / 128 * 64, scale_bf16, (K + 127) / 128, (hipStream_t)stream));
+}
+
+int anyref_op_dequant_int4(void* stream, const uint8_t* q, const void* scale_bf16, int N, int K, void* out_bf16) {
+  OP_GUARD(launch_dequant_int4_rows(q, (K + 127) / 128 * 64, scale_bf16, (K + 127) / 128, N, K, out_bf16, K, (hipStream_t)stream));
+}
+
+int anyref_op_gemv_int4(void* stream, const float* x, const float* gain, float eps, const uint8_t* W, const uint8_t* W2,
+                        const void* scale_bf16, const void* scale2_bf16, float* y, const float* resid, int B, int N, int K) {
+  OP_GUARD({
+    GemvArgs a;
+    a.x = x; a.ldx = K; a.gain = gain; a.eps = eps; a.W = W; a.W2 = W2; a.gscale = scale_bf16; a.gscale2 = scale2_bf16;
+    a.w_int4 = 1; a.ldw = (K + 127) / 128 * 64; a.ld_gscale = (K + 127) / 128; a.y = y; a.resid = resid; a.ldy = N; a.B = B;
+    a.N = N; a.K = K;
+    launch_gemv<bf16>(a, (hipStream_t)stream);
+  });
+}
+
 int anyref_op_iou_counts(void* stream, const float* logits, const uint8_t* target, int n, int64_t hw,
                          int64_t* counts) {
   OP_GUARD(launch_iou_counts(logits, target, n, hw, counts, (hipStream_t)stream));

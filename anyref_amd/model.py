@@ -92,7 +92,7 @@ class AnyRefForCausalLM:
         self.cfg = cfg
         self.mode = {"parity": _lib.MODE_PARITY, "perf": _lib.MODE_PERF, "perf_fp8w": _lib.MODE_PERF_FP8W,
                      "parity16": _lib.MODE_PARITY16, "perf_f16": _lib.MODE_PERF_F16,
-                     "parity16_f16": _lib.MODE_PARITY16_F16}[mode]
+                     "parity16_f16": _lib.MODE_PARITY16_F16, "perf_int4w": _lib.MODE_PERF_INT4W}[mode]
         self.mode_name = mode
         self.device_index = device
         self.device = torch.device("cuda", device)

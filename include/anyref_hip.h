@@ -63,6 +63,16 @@ extern "C" {
  * SwiGLU hidden row, image patch) past +-65504 becomes inf in its hi term and shows as NaN outputs; the reference's fp16 run
  * has the same limit on more tensors. */
 #define ANYREF_MODE_PARITY16_F16 5
+/* PERF with q/k/v/o and gate/up/down of every LLaMA layer held as 4-bit integers with one bf16 scale per group of 128
+ * consecutive k of an output row (weight-only, quantised at finalize; the last group of a row may be short).  Per group:
+ * amax = max|w|; amax < 2^-100: s = 1, q = 0; else s = amax / 7 (f32) rounded UP to 5 significant bits (a bf16 with three zero
+ * low mantissa bits, amax / 7 <= s <= 1.0625 amax / 7), q = clamp(rne(w / s), -7, 7), held value w' = q * s -- exactly a bf16,
+ * so the decode GEMV (sum_g s_g sum_k q_k x_k) and the prefill GEMM (a bf16 image of w') multiply one set of weights.
+ * lm_head, the embeddings, the vision / audio towers, SAM and every activation stay as in PERF.  About 0.52 bytes per LLM
+ * linear element instead of 2.  llm_dim and llm_mlp must be multiples of 16 (finalize fails, naming the tensor).
+ * A byte / accuracy trade (relative rms weight error 0.12 - 0.15 on Gaussian weights), not a parity mode;
+ * anyref_amd/quant.py states the format in torch. */
+#define ANYREF_MODE_PERF_INT4W (6)
 
 typedef struct anyref_config {
   int32_t abi_version; /* = ANYREF_ABI_VERSION */
@@ -296,7 +306,8 @@ int64_t anyref_device_bytes(anyref_handle* h);
 /* Name of the compute mode's arithmetic ("f32" / "bf16" / "f16" ...). */
 const char* anyref_mode_name(anyref_handle* h);
 /* After anyref_finalize, in every mode: *out = the number of weight elements the handle holds in a value other than the one
- * handed to anyref_set_weight (rounded to the mode's 16-bit type, or quantised to fp8 and back in ANYREF_MODE_PERF_FP8W).
+ * handed to anyref_set_weight (rounded to the mode's 16-bit type, or quantised to fp8 and back in ANYREF_MODE_PERF_FP8W, or to int4
+ * groups and back in ANYREF_MODE_PERF_INT4W).
  * 0 in PARITY; 0 in PERF_F16 for an fp16 checkpoint; in PERF that checkpoint loses 3 mantissa bits in most elements. */
 int anyref_inexact_weights(anyref_handle* h, int64_t* out);
 

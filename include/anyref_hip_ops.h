@@ -69,6 +69,14 @@ int anyref_op_gemm_fp8(void* stream, const void* A, const uint8_t* W8, const flo
 int anyref_op_gemv_fp8(void* stream, const float* x, const float* gain, float eps, const uint8_t* W,
                        const uint8_t* W2, const float* scale, const float* scale2, float* y, const float* resid,
                        int B, int N, int K);
+/* int4 group quantisation used by ANYREF_MODE_PERF_INT4W: src f32 [N,K] (K % 16 == 0) -> nibble rows q u8 [N, ceil(K/128) * 64]
+ * (the order of the nibbles inside a 16-byte block is the library's) and scales bf16 [N, ceil(K/128)] */
+int anyref_op_quant_int4(void* stream, const float* src, int N, int K, uint8_t* q, void* scale_bf16);
+/* q, scale as written by anyref_op_quant_int4 -> out bf16 [N,K] = q * scale (exact) */
+int anyref_op_dequant_int4(void* stream, const uint8_t* q, const void* scale_bf16, int N, int K, void* out_bf16);
+/* decode GEMV on int4 weights: y[b,n] = sum_g scale[n,g] * sum_{k in g} bf16(norm(x))[b,k] * q[n,k] (SwiGLU pair if W2) (+ resid) */
+int anyref_op_gemv_int4(void* stream, const float* x, const float* gain, float eps, const uint8_t* W, const uint8_t* W2,
+                        const void* scale_bf16, const void* scale2_bf16, float* y, const float* resid, int B, int N, int K);
 /* SURVEY.md §8 f-2, replaces `(torch.sigmoid(pred) > 0.5).int()` + utils/utils.py:79-91
  * intersectionAndUnionGPU(pred, gt, 2, ignore_index=255) (call site eval_referseg.py:189-208):
  * logits f32 [n, hw] (device), target u8 [n, hw] with values 0 / 1 / 255 (device), counts i64 [n, 6]

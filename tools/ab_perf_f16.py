@@ -31,7 +31,7 @@ from anyref_amd.model import AnyRefForCausalLM  # noqa: E402
 from anyref_amd.synth import synth_state_dict  # noqa: E402
 
 MODES = ("perf", "perf_f16")
-TOKEN = {"parity": "f32", "perf": "bf16", "perf_fp8w": "fp8w", "perf_f16": "f16", "parity16": "sp16", "parity16_f16": "sp16h"}
+TOKEN = {"parity": "f32", "perf": "bf16", "perf_fp8w": "fp8w", "perf_f16": "f16", "parity16": "sp16", "parity16_f16": "sp16h", "perf_int4w": "int4w"}
 T_NEW = 10
 
 
