@@ -4,20 +4,9 @@
 #include <stdexcept>
 #include <type_traits>
 
-#include "kernels.h"
+#include "gemv_common.h"
 
 namespace anyref {
-
-// ANYREF_GEMV_GRID=n: decode GEMV workgroups (measurement knob, read once; never set in production)
-// ANYREF_GEMV_PAIR=0: one wave per row group (the round-2 work split) instead of wave pairs sharing a group's K chunks
-static bool gemv_pair_knob() {
-  static const bool p = !(getenv("ANYREF_GEMV_PAIR") && atoi(getenv("ANYREF_GEMV_PAIR")) == 0);
-  return p;
-}
-static int gemv_grid_knob() {
-  static const int g = getenv("ANYREF_GEMV_GRID") ? atoi(getenv("ANYREF_GEMV_GRID")) : 0;
-  return g;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Decode GEMV: weight-streaming, HBM-bound.  One workgroup (8 waves) stages the (optionally
@@ -62,42 +51,25 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
   __shared__ float red2[2][4][2][NB];  // PAIR: partial sums of the odd waves, double-buffered over the groups
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K;
-  // kernel-side timestamps (kernels.h: StampArgs): off in production (one uniform branch)
   __shared__ unsigned long long st_t[2];
   __shared__ unsigned st_cnt;
-  unsigned long long t_begin = 0;
-  if (a.stamp.base) {
-    t_begin = wall_clock64();
-    if (tid == 0) {
-      st_t[0] = ~0ull;
-      st_t[1] = 0;
-      st_cnt = 0;
-    }
-  }
+  const unsigned long long t_begin = gemv_stamp_begin(a.stamp, st_t, st_cnt, tid);
 
   const WT* __restrict__ W = reinterpret_cast<const WT*>(a.W);
   const WT* __restrict__ W2 = reinterpret_cast<const WT*>(a.W2);
   const int ldw = a.ldw > 0 ? a.ldw : K;  // 2K: gate / up rows interleaved in one matrix
-  const int nwaves = gridDim.x * 8;
-  const int gw = blockIdx.x * 8 + wave;
-  const int ngroups = cdiv(a.N, R);
   constexpr int CH = 64 * VN * UNR;  // K elements one wave sweeps per chunk
-  const int nch = cdiv(K, CH);
-  // Flattened (row group, K chunk) work list of this wave, software-pipelined one chunk deep: the
-  // loads of item t+1 are in flight while item t is multiplied (and while x is being staged).
-  const int unit = PAIR ? gw >> 1 : gw, nunits = PAIR ? nwaves >> 1 : nwaves, half = PAIR ? (gw & 1) : 0;
-  const int nchp = PAIR ? (nch + 1) >> 1 : nch;  // chunk slots per wave and group
-  // (PAIR: every wave walks the same number of groups -- they all meet at the hand-off barrier)
-  const int my_groups = PAIR ? cdiv(ngroups, nunits) : (gw < ngroups ? (ngroups - gw + nwaves - 1) / nwaves : 0);
-  const int items = my_groups * nchp;
+  // the wave's work list, software-pipelined one chunk deep: the loads of item t+1 are in flight while item t is multiplied
+  // (and while x is being staged)
+  const GemvWork<R, PAIR> wk(gridDim.x, blockIdx.x, wave, a.N, cdiv(K, CH));
+  const int items = wk.items;
   uint4v wcur[UNR][RW], wnxt[UNR][RW];
   auto load_item = [&](int t, uint4v (&w)[UNR][RW]) {
-    const int g = unit + (t / nchp) * nunits, c = PAIR ? 2 * (t % nchp) + half : t % nchp;
-    const int n0 = g * R;
-    const bool live = !PAIR || (g < ngroups && c < nch);
+    const auto it = wk.item(t);
+    const int n0 = it.g * R;
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
-      const int k = live ? c * CH + u * 64 * VN + lane * VN : K;
+      const int k = it.live ? it.c * CH + u * 64 * VN + lane * VN : K;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int n = n0 + r < a.N ? n0 + r : a.N - 1;
@@ -109,9 +81,7 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
                              : uint4v{0, 0, 0, 0};
     }
   };
-  // x goes FIRST into the (in-order) vector-memory queue: its wait then leaves the weight prefetch
-  // issued right behind it in flight.  Issued the other way round, the x wait also waited for the
-  // first weight chunk (measured: x staged 4-9 us into a 10-22 us kernel).
+  // x goes FIRST into the (in-order) vector-memory queue, the first weight chunk right behind it (gemv_common.h)
   if (!a.gain) {
     // no RMSNorm (o_proj / down_proj inputs): a plain f32 -> T copy with 16-byte loads.  The register
     // path below issues XPT predicated dword loads per thread; at K = 11008 (XPT = 24) that staging
@@ -141,42 +111,11 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
     // RMSNorm path: x and the gain as 16-byte loads (XV per thread and row; launch_gemv checks the alignment) -- dword
     // loads were XPT per row: 40 load instructions per thread at 4 batch rows in front of the first weight load
     constexpr int XV = (XPT + 3) / 4;  // float4 per thread
-    float4v xr[NB][XV], gr[XV];
-#pragma unroll
-    for (int i = 0; i < XV; ++i) {
-      const int k = (tid + i * 512) * 4;
-      gr[i] = k < K ? *reinterpret_cast<const float4v*>(a.gain + k) : float4v{1.f, 1.f, 1.f, 1.f};
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const float* x = a.x + (int64_t)(b0 + (b < nb ? b : 0)) * a.ldx;
-#pragma unroll
-      for (int i = 0; i < XV; ++i) {
-        const int k = (tid + i * 512) * 4;
-        xr[b][i] = (b < nb && k < K) ? *reinterpret_cast<const float4v*>(x + k) : float4v{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+    GemvNormStage<NB, XV> st;
+    st.load(a, b0, nb, tid);
     if (items > 0) load_item(0, wcur);
-    // sums of squares of ALL batch rows behind ONE barrier (a barrier per row: NB dependent LDS round trips per launch)
     float scale[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < XV; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ss += xr[b][i][e] * xr[b][i][e];
-      ss = wave_sum(ss);
-      if (lane == 0) red[b][wave] = ss;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      float tot = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) tot += red[b][w];
-      scale[b] = rsqrtf(tot / (float)K + a.eps);
-    }
+    st.scales(a, red, lane, wave, scale);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       if (b >= nb) continue;
@@ -184,15 +123,13 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
       for (int i = 0; i < XV; ++i) {
         const int k = (tid + i * 512) * 4;
         if (k < K) {
-          const float4v v = xr[b][i] * scale[b] * gr[i];
+          const float4v v = st.xr[b][i] * scale[b] * st.gr[i];
           store4_from_f32<XE>(&xs[b * K + k], v[0], v[1], v[2], v[3]);
-          // the normalised row itself is an output of the step (last-layer hidden state before lm_head)
-          if (a.xn_out && blockIdx.x == 0)
-            *reinterpret_cast<float4v*>(a.xn_out + (int64_t)(a.xn_row_map ? a.xn_row_map[b0 + b] : b0 + b) * a.xn_ld + k) = v;
+          gemv_store_xn(a, b0 + b, k, v);
         }
       }
     }
-}
+  }
   __syncthreads();
 
   float acc[RW][NB];
@@ -202,11 +139,10 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
     for (int b = 0; b < NB; ++b) acc[r][b] = 0.f;
   for (int t = 0; t < items; ++t) {
     if (t + 1 < items) load_item(t + 1, wnxt);
-    const int ci = t % nchp, c = PAIR ? 2 * ci + half : ci;
-    const bool live = !PAIR || (unit + (t / nchp) * nunits < ngroups && c < nch);
+    const auto it = wk.item(t);
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
-      const int k = live ? c * CH + u * 64 * VN + lane * VN : K;
+      const int k = it.live ? it.c * CH + u * 64 * VN + lane * VN : K;
       if (k < K) {
         if constexpr (DOT2) {
           // 16-bit weights with more than one batch row: both operands stay PACKED (8 bf16 per 16 bytes) and go through
@@ -262,63 +198,7 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
         }
       }
     }
-    if (ci == nchp - 1) {  // row group finished: reduce across the wave and store
-      const int n0 = (unit + (t / nchp) * nunits) * R;
-#pragma unroll
-      for (int r = 0; r < RW; ++r)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[r][b] = wave_sum(acc[r][b]);
-      if constexpr (PAIR) {
-        const int buf = (t / nchp) & 1;
-        if (half == 1 && lane == 0) {
-#pragma unroll
-          for (int r = 0; r < RW; ++r)
-#pragma unroll
-            for (int b = 0; b < NB; ++b) red2[buf][wave >> 1][r][b] = acc[r][b];
-        }
-        __syncthreads();
-        if (half == 0) {
-#pragma unroll
-          for (int r = 0; r < RW; ++r)
-#pragma unroll
-            for (int b = 0; b < NB; ++b) acc[r][b] += red2[buf][wave >> 1][r][b];
-        }
-      }
-      // Every lane holds every reduced sum (xor butterfly): lane i < R * NB finishes output (r, b) = (i / NB, i % NB) --
-      // scale / bias / activation / residual load / store side by side.  One lane walking the R * NB outputs is a chain of
-      // dependent residual load -> store round trips (y may alias the residual, so the compiler keeps their order): 8 per
-      // row group at 4 batch rows, on the wave's critical path at the end of the launch.
-      if (lane < R * NB && half == 0) {
-        const int r = lane / NB, b = lane % NB, n = n0 + r;
-        float v = 0.f, v2 = 0.f;
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr)
-#pragma unroll
-          for (int bb = 0; bb < NB; ++bb)
-            if (lane == rr * NB + bb) {
-              v = acc[rr][bb];
-              v2 = DUAL ? acc[RW - 1][bb] : 0.f;
-            }
-        if (n < a.N && b < nb) {
-          if constexpr (W8) {
-            v *= a.wscale[(int64_t)n * a.ws_stride];
-            if (DUAL) v2 *= a.wscale2[(int64_t)n * a.ws_stride];
-          }
-          if (a.bias) v += a.bias[n];
-          if (DUAL)
-            v = apply_act(v, ACT_SILU) * v2;
-          else
-            v = apply_act(v, a.act);
-          const int64_t o = (int64_t)(b0 + b) * a.ldy + n;
-          if (a.resid) v += a.resid[o];
-          a.y[o] = v;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < RW; ++r)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[r][b] = 0.f;
-    }
+    if (it.last) gemv_finish_group<NB, R, DUAL, W8, PAIR>(a, acc, red2, it.g, it.pass, wk.half, lane, wave, b0, nb);
     if (t + 1 < items) {
 #pragma unroll
       for (int u = 0; u < UNR; ++u)
@@ -326,22 +206,8 @@ __global__ __launch_bounds__(512) void gemv_kernel(GemvArgs a, int b0, int nb) {
         for (int r = 0; r < RW; ++r) wcur[u][r] = wnxt[u][r];
     }
   }
-  if (a.stamp.base && lane == 0) {
-    // every wave folds its span into the workgroup's (LDS atomics; the init is ordered by the barrier after the x
-    // stage); the wave whose count comes back last has seen all of them and writes the workgroup's slot
-    atomicMin(&st_t[0], t_begin);
-    atomicMax(&st_t[1], (unsigned long long)wall_clock64());
-    if (atomicAdd(&st_cnt, 1u) == 7u) {
-      const int e = *a.stamp.epoch;
-      if (e < a.stamp.max_epoch) {
-        unsigned long long* p = a.stamp.base + (size_t)e * a.stamp.stride + (size_t)blockIdx.x * 2;
-        p[0] = st_t[0];
-        p[1] = st_t[1];
-      }
-    }
-  }
+  gemv_stamp_end(a.stamp, st_t, st_cnt, t_begin, lane);
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // Decode GEMV for 5 - 8 batch rows (bf16 activations; bf16 or fp8 weights), ONE pass over the weights.
@@ -439,51 +305,20 @@ __global__ __launch_bounds__(512) void gemv_rows8_kernel(GemvArgs a, int b0, int
 #pragma unroll
   for (int b = 0; b < NB; ++b) scale[b] = 1.f;
   if (a.gain) {
-    // RMSNorm inputs (one K stage): rows through registers, sums of squares of all rows behind one barrier
-    float4v xr[NB][XV], gr[XV];
-#pragma unroll
-    for (int i = 0; i < XV; ++i) {
-      const int k = (tid + i * 512) * 4;
-      gr[i] = k < K ? *reinterpret_cast<const float4v*>(a.gain + k) : float4v{1.f, 1.f, 1.f, 1.f};
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const float* x = a.x + (int64_t)(b0 + (b < nb ? b : 0)) * a.ldx;
-#pragma unroll
-      for (int i = 0; i < XV; ++i) {
-        const int k = (tid + i * 512) * 4;
-        xr[b][i] = (b < nb && k < K) ? *reinterpret_cast<const float4v*>(x + k) : float4v{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+    // RMSNorm inputs (one K stage): rows through registers (gemv_common.h)
+    GemvNormStage<NB, XV> st;
+    st.load(a, b0, nb, tid);
     first_chunks();
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < XV; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ss += xr[b][i][e] * xr[b][i][e];
-      ss = wave_sum(ss);
-      if (lane == 0) red[b][wave] = ss;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      float tot = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) tot += red[b][w];
-      scale[b] = rsqrtf(tot / (float)K + a.eps);
-    }
+    st.scales(a, red, lane, wave, scale);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
 #pragma unroll
       for (int i = 0; i < XV; ++i) {
         const int k = (tid + i * 512) * 4;
         if (k < K) {
-          const float4v v = xr[b][i] * scale[b] * gr[i];  // rows >= nb: zeros
+          const float4v v = st.xr[b][i] * scale[b] * st.gr[i];  // rows >= nb: zeros
           store4_from_f32<bf16>(reinterpret_cast<bf16*>(smem + xpos(b, k)), v[0], v[1], v[2], v[3]);
-          if (a.xn_out && blockIdx.x == 0 && b < nb)
-            *reinterpret_cast<float4v*>(a.xn_out + (int64_t)(a.xn_row_map ? a.xn_row_map[b0 + b] : b0 + b) * a.xn_ld + k) = v;
+          gemv_store_xn(a, b0 + b, k, v, b < nb);
         }
       }
     }
@@ -585,17 +420,7 @@ __global__ __launch_bounds__(512) void gemv_rows8_kernel(GemvArgs a, int b0, int
         for (int r = 0; r < R; ++r) {
           const int n = g * R + r;
           if (n >= a.N) continue;
-          float o = v[r], o2 = DUAL ? v[r + 2] : 0.f;
-          if constexpr (W8) {
-            o *= a.wscale[(int64_t)n * a.ws_stride];
-            if (DUAL) o2 *= a.wscale2[(int64_t)n * a.ws_stride];
-          }
-          if (a.bias) o += a.bias[n];
-          if (DUAL) o = apply_act(o, ACT_SILU) * o2;
-          else o = apply_act(o, a.act);
-          const int64_t off = (int64_t)(b0 + b) * a.ldy + n;
-          if (a.resid) o += a.resid[off];
-          a.y[off] = o;
+          gemv_epilogue<DUAL, W8>(a, v[r], DUAL ? v[r + 2] : 0.f, n, b0 + b);
         }
       }
     }
@@ -656,12 +481,8 @@ static bool gemv_rows8_launch(const GemvArgs& a, int b0, int nb, hipStream_t s) 
   snprintf(tag, sizeof(tag), "gemv_rows8_%s%s", w8 ? "fp8w" : "bf16", dual ? "_swiglu" : "");
   ProfScope prof(tag, 2.0 * nb * a.N * (double)a.K * (dual ? 2 : 1), wbytes, s);
   auto launch = [&](auto w8_t, auto dual_t, auto xv_t) {
-    constexpr bool W8 = decltype(w8_t)::value, DUAL = decltype(dual_t)::value;
-    constexpr int XV = decltype(xv_t)::value;
-    auto kern = &gemv_rows8_kernel<W8, DUAL, XV>;
-    static KernelAttrOnce once;
-    ensure_dyn_lds(once, reinterpret_cast<const void*>(kern), 152 * 1024);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, b0, nb, kh0, rs);
+    gemv_launch<&gemv_rows8_kernel<decltype(w8_t)::value, decltype(dual_t)::value, decltype(xv_t)::value>, 152 * 1024>(
+        grid, lds, s, a, b0, nb, kh0, rs);
   };
   using TT = std::true_type;
   using FF = std::false_type;
@@ -682,63 +503,22 @@ static bool gemv_rows8_launch(const GemvArgs& a, int b0, int nb, hipStream_t s) 
 }
 
 template <typename T, int NB>
-static void gemv_dispatch(const GemvArgs& a_in, int b0, int nb, hipStream_t s) {
-  GemvArgs a = a_in;
+static void gemv_dispatch(const GemvArgs& a, int b0, int nb, hipStream_t s) {
   const size_t lds = (size_t)NB * a.K * (is_split<T>::value ? 4 : sizeof(T));
-  if (lds > 150 * 1024) throw std::runtime_error("gemv: K too large for the LDS activation stage");
-  // one or two 8-wave workgroups per CU depending on the LDS the activation stage needs
-  // (512 workgroups measured best for N*K of 34-262 MB; 256 / 1024 / 2048 were 3-30 % slower)
-  int grid = 256 * (lds > 76 * 1024 ? 1 : 2);
-  const int grid_rule = grid;  // (the wave-pair decision below goes by this one: the same sums whatever grid is asked for)
-  if (a.grid > 0 && a.grid < grid) grid = a.grid;
-  if (gemv_grid_knob() > 0) grid = gemv_grid_knob();
-  auto go = [&](auto xpt_tag) {
-    constexpr int XPT = decltype(xpt_tag)::value;
-    // algorithmic bytes: every weight element once (+ the tiny activation / output vectors)
-    const double wsz = a.w_fp8 ? 1.0 : (is_split<T>::value ? 2.0 : (double)sizeof(T));
-    const double wbytes = (double)a.N * a.K * wsz * (a.W2 ? 2 : 1) + (double)nb * (a.K + a.N) * 4;
-    // one tag per kernel instantiation, so a tag's average can be checked against rocprofv3's per-kernel one
-    char tag[40];
-    snprintf(tag, sizeof(tag), "gemv_%s%s_x%d",
-             a.w_fp8 ? "fp8w" : (is_split<T>::value ? (is_half16<typename split_term<T>::type>::value ? "sp16h" : "sp16") : is_half16<T>::value ? "f16" : sizeof(T) == 2 ? "bf16" : "f32"),
-             a.W2 ? "_swiglu" : "", XPT);
-    ProfScope prof(tag, 2.0 * nb * a.N * (double)a.K * (a.W2 ? 2 : 1), wbytes, s);
-    if (g_stamp && g_stamp->on) a.stamp = g_stamp->slot(tag, wbytes, grid);
-    auto launch = [&](auto dual_t, auto w8_t, auto pair_t) {
-      constexpr bool DUAL = decltype(dual_t)::value, W8 = decltype(w8_t)::value, PAIR = decltype(pair_t)::value;
-      auto kern = &gemv_kernel<T, NB, DUAL, XPT, W8, PAIR>;
-      static KernelAttrOnce once;  // per instantiation, per device
-      ensure_dyn_lds(once, reinterpret_cast<const void*>(kern), 150 * 1024);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, b0, nb);
-    };
-    using TT = std::true_type;
-    using FF = std::false_type;
-    // wave pairs where single waves would leave half of the grid without a row group (N = 4096 at 7B: o_proj 8.5 ->
-    // 8.05 us, down_proj 17.45 -> 16.7 us); with more groups than waves the plain split is faster (qkv 17.9 vs 18.8 us,
-    // gate/up 30.9 vs 31.6: the hand-off barrier per group costs more than the better balance returns)
-    const bool pair = gemv_pair_knob() && cdiv(a.N, a.W2 ? 1 : 2) * 2 <= (gemv_grid_knob() > 0 ? grid : grid_rule) * 8;
-    auto by_pair = [&](auto dual_t, auto w8_t) {
-      if (pair) launch(dual_t, w8_t, TT());
-      else launch(dual_t, w8_t, FF());
-    };
+  const double wsz = a.w_fp8 ? 1.0 : (is_split<T>::value ? 2.0 : (double)sizeof(T));
+  const double wbytes = (double)a.N * a.K * wsz * (a.W2 ? 2 : 1) + (double)nb * (a.K + a.N) * 4;
+  const char* kind = a.w_fp8 ? "fp8w" : (is_split<T>::value ? (is_half16<typename split_term<T>::type>::value ? "sp16h" : "sp16") : is_half16<T>::value ? "f16" : sizeof(T) == 2 ? "bf16" : "f32");
+  gemv_dispatch_pass("gemv", kind, a, lds, wbytes, nb, s, [&](auto xpt_t, auto dual_t, auto pair_t, const GemvArgs& g, int grid) {
+    constexpr int XPT = decltype(xpt_t)::value;
+    constexpr bool DUAL = decltype(dual_t)::value, PAIR = decltype(pair_t)::value;
     if constexpr (std::is_same<T, bf16>::value) {
-      if (a.w_fp8) {
-        if (a.W2) by_pair(TT(), TT());
-        else by_pair(FF(), TT());
+      if (g.w_fp8) {
+        gemv_launch<&gemv_kernel<T, NB, DUAL, XPT, true, PAIR>>(grid, lds, s, g, b0, nb);
         return;
       }
     }
-    if (a.W2) by_pair(TT(), FF());
-    else by_pair(FF(), FF());
-  };
-  if (a.K <= 512 * 8)
-    go(std::integral_constant<int, 8>());
-  else if (a.K <= 512 * 24)
-    go(std::integral_constant<int, 24>());
-  else if (a.K <= 512 * 32)
-    go(std::integral_constant<int, 32>());
-  else
-    throw std::runtime_error("gemv: K > 16384 not supported");
+    gemv_launch<&gemv_kernel<T, NB, DUAL, XPT, false, PAIR>>(grid, lds, s, g, b0, nb);
+  });
 }
 
 template <typename T>
@@ -755,25 +535,17 @@ void launch_gemv(const GemvArgs& a, hipStream_t s) {
   if (((uintptr_t)a.x & 15) || a.ldx % 4 || a.K % 4 || (a.gain && ((uintptr_t)a.gain & 15)) ||
       (a.xn_out && (((uintptr_t)a.xn_out & 15) || a.xn_ld % 4)))
     throw std::runtime_error("gemv: x / gain / xn_out rows must be 16-byte aligned");
-  constexpr int NBMAX = sizeof(T) == 2 ? 4 : 2;
-  for (int b0 = 0; b0 < a.B;) {
-    const int left = a.B - b0;
-    if constexpr (std::is_same<T, bf16>::value) {
-      // 5 - 8 rows left: one pass over the weights on the 4 x 4 x 4 MFMA form where the shape allows
-      if (left > 4 && gemv_rows8_launch(a, b0, left < 8 ? left : 8, s)) {
-        b0 += left < 8 ? left : 8;
-        continue;
-      }
+  int b0 = 0;
+  if constexpr (std::is_same<T, bf16>::value) {
+    // while 5 or more rows are left: 8 (or what is left) in one pass over the weights on the 4 x 4 x 4 MFMA form, where the
+    // shape allows (the launcher refuses by shape alone, so a refusal holds for the rest of the rows)
+    while (a.B - b0 > 4) {
+      const int n8 = a.B - b0 < 8 ? a.B - b0 : 8;
+      if (!gemv_rows8_launch(a, b0, n8, s)) break;
+      b0 += n8;
     }
-    const int nb = left < NBMAX ? left : NBMAX;
-    if (nb == 1)
-      gemv_dispatch<T, 1>(a, b0, nb, s);
-    else if (nb == 2)
-      gemv_dispatch<T, 2>(a, b0, nb, s);
-    else
-      gemv_dispatch<T, NBMAX>(a, b0, nb, s);
-    b0 += nb;
   }
+  gemv_passes<sizeof(T) == 2 ? 4 : 2>(b0, a.B, [&](auto nb_t, int p0, int nb) { gemv_dispatch<T, decltype(nb_t)::value>(a, p0, nb, s); });
 }
 template void launch_gemv<float>(const GemvArgs&, hipStream_t);
 
@@ -789,12 +561,9 @@ void launch_gemv_skinny_f32(const GemvArgs& a, hipStream_t s) {
   const int grid = ngroups >= 2048 ? 512 : cdiv(ngroups, 4);  // a wave pair per row group
   auto go = [&](auto nb_tag) {
     constexpr int NB = decltype(nb_tag)::value;
-    auto kern = &gemv_kernel<float, NB, false, 8, false, true>;
-    static KernelAttrOnce once;
-    ensure_dyn_lds(once, reinterpret_cast<const void*>(kern), 150 * 1024);
     ProfScope prof("gemv_f32_skinny", 2.0 * a.B * a.N * (double)a.K, (double)a.N * a.K * 4 + (double)a.B * (a.K + a.N) * 4,
                    s);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)NB * a.K * sizeof(float), s, a, 0, a.B);
+    gemv_launch<&gemv_kernel<float, NB, false, 8, false, true>>(grid, (size_t)NB * a.K * sizeof(float), s, a, 0, a.B);
   };
   if (a.B == 1) go(std::integral_constant<int, 1>());
   else if (a.B == 2) go(std::integral_constant<int, 2>());

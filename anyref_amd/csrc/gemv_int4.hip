@@ -15,7 +15,7 @@
 #include <stdexcept>
 #include <type_traits>
 
-#include "kernels.h"
+#include "gemv_common.h"
 
 namespace anyref {
 
@@ -115,9 +115,11 @@ void launch_dequant_int4_rows(const uint8_t* q, int ldq, const void* scale_bf16,
 }
 
 // ---------------------------------------------------------------------------------------------
-// Decode GEMV on int4 weights; the contract of gemv_kernel (gemv.hip): x staged first (optional RMSNorm, xn_out), as bf16 in
-// LDS; weights by 16-byte non-temporal loads straight to VGPRs, software-pipelined one chunk deep; 1 - 4 batch rows per pass;
-// the DUAL gate / up SwiGLU form; bias / act / resid; wave pairs where single waves would leave half the grid idle; stamps.
+// Decode GEMV on int4 weights.  What it shares with gemv_kernel (gemv.hip) is gemv_common.h's code, not a copy: the work list
+// with the wave-pair split, the RMSNorm input stage (x first, the first weight chunk right behind it; xn_out), the row-group
+// finish (DUAL gate / up SwiGLU form, bias / act / resid), the stamps, and on the host the grid / wave-pair rules, the K ladder
+// and the passes of 1 - 4 batch rows.  Its own: x as bf16 planes + block sums in LDS, and the multiply.  Weights by 16-byte
+// non-temporal loads straight to VGPRs, software-pipelined one chunk deep.
 //
 // A lane's 16 bytes are one BLOCK: 32 weights of one group.  A row of K = 4096 is two wave-loads, K = 11008 is 5.4, so a
 // chunk is UNR = 1 .. 4 wave-loads (by K) instead of gemv_kernel's four loads of 512 weights.
@@ -146,38 +148,23 @@ __global__ __launch_bounds__(512) void gemv_int4_kernel(GemvArgs a, int b0, int 
   float* xsum = reinterpret_cast<float*>(smem + (size_t)NB * row_bytes);  // [NB][KB]
   __shared__ unsigned long long st_t[2];
   __shared__ unsigned st_cnt;
-  unsigned long long t_begin = 0;
-  if (a.stamp.base) {
-    t_begin = wall_clock64();
-    if (tid == 0) {
-      st_t[0] = ~0ull;
-      st_t[1] = 0;
-      st_cnt = 0;
-    }
-  }
+  const unsigned long long t_begin = gemv_stamp_begin(a.stamp, st_t, st_cnt, tid);
 
   const uint8_t* __restrict__ W = reinterpret_cast<const uint8_t*>(a.W);
   const uint8_t* __restrict__ W2 = reinterpret_cast<const uint8_t*>(a.W2);
   const uint16_t* __restrict__ S = reinterpret_cast<const uint16_t*>(a.gscale);
   const uint16_t* __restrict__ S2 = reinterpret_cast<const uint16_t*>(a.gscale2);
   const int ldw = a.ldw, lgs = a.ld_gscale;  // bytes between nibble rows, scales between scale rows
-  const int nwaves = gridDim.x * 8;
-  const int gw = blockIdx.x * 8 + wave;
-  const int ngroups = cdiv(a.N, R);
-  const int nch = cdiv(KB, CHB);
-  const int unit = PAIR ? gw >> 1 : gw, nunits = PAIR ? nwaves >> 1 : nwaves, half = PAIR ? (gw & 1) : 0;
-  const int nchp = PAIR ? (nch + 1) >> 1 : nch;  // chunk slots per wave and group
-  const int my_groups = PAIR ? cdiv(ngroups, nunits) : (gw < ngroups ? (ngroups - gw + nwaves - 1) / nwaves : 0);
-  const int items = my_groups * nchp;
+  const GemvWork<R, PAIR> wk(gridDim.x, blockIdx.x, wave, a.N, cdiv(KB, CHB));
+  const int items = wk.items;
   uint4v wcur[UNR][RW], wnxt[UNR][RW];
   uint32_t scur[UNR][RW], snxt[UNR][RW];  // the block's group scale (bf16 bits), loaded beside it
   auto load_item = [&](int t, uint4v (&w)[UNR][RW], uint32_t (&sc)[UNR][RW]) {
-    const int g = unit + (t / nchp) * nunits, c = PAIR ? 2 * (t % nchp) + half : t % nchp;
-    const int n0 = g * R;
-    const bool live = !PAIR || (g < ngroups && c < nch);
+    const auto it = wk.item(t);
+    const int n0 = it.g * R;
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
-      const int blk = live ? c * CHB + u * 64 + lane : KB;
+      const int blk = it.live ? it.c * CHB + u * 64 + lane : KB;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int n = n0 + r < a.N ? n0 + r : a.N - 1;
@@ -195,54 +182,20 @@ __global__ __launch_bounds__(512) void gemv_int4_kernel(GemvArgs a, int b0, int 
   // ---- x stage: x goes FIRST into the (in-order) vector-memory queue, the first weight chunk right behind it ----
   {
     constexpr int XV = (XPT + 3) / 4;  // float4 per thread and row
-    float4v xr[NB][XV], gr[XV];
-    if (a.gain) {
-#pragma unroll
-      for (int i = 0; i < XV; ++i) {
-        const int k = (tid + i * 512) * 4;
-        gr[i] = k < K ? *reinterpret_cast<const float4v*>(a.gain + k) : float4v{1.f, 1.f, 1.f, 1.f};
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const float* x = a.x + (int64_t)(b0 + (b < nb ? b : 0)) * a.ldx;
-#pragma unroll
-      for (int i = 0; i < XV; ++i) {
-        const int k = (tid + i * 512) * 4;
-        xr[b][i] = (b < nb && k < K) ? *reinterpret_cast<const float4v*>(x + k) : float4v{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+    GemvNormStage<NB, XV> st;
+    if (a.gain) st.load_gain(a, tid);
+    st.load_x(a, b0, nb, tid);
     if (items > 0) load_item(0, wcur, scur);
     float scale[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) scale[b] = 1.f;
-    if (a.gain) {
-      // sums of squares of ALL batch rows behind ONE barrier
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < XV; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ss += xr[b][i][e] * xr[b][i][e];
-        ss = wave_sum(ss);
-        if (lane == 0) red[b][wave] = ss;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        float tot = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) tot += red[b][w];
-        scale[b] = rsqrtf(tot / (float)K + a.eps);
-      }
-    }
+    if (a.gain) st.scales(a, red, lane, wave, scale);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
 #pragma unroll
       for (int i = 0; i < XV; ++i) {
         const int k = (tid + i * 512) * 4;  // eight consecutive lanes hold one block
-        const float4v v = a.gain ? xr[b][i] * scale[b] * gr[i] : xr[b][i];  // zeros past K and for rows >= nb
+        const float4v v = a.gain ? st.xr[b][i] * scale[b] * st.gr[i] : st.xr[b][i];  // zeros past K and for rows >= nb
         const bf16 h0 = f2bf(v[0]), h1 = f2bf(v[1]), h2 = f2bf(v[2]), h3 = f2bf(v[3]);
         float sum = (bf2f(h0) + bf2f(h1)) + (bf2f(h2) + bf2f(h3));
         sum += __shfl_xor(sum, 1, 64);
@@ -253,9 +206,7 @@ __global__ __launch_bounds__(512) void gemv_int4_kernel(GemvArgs a, int b0, int 
           char* p = smem + (size_t)b * row_bytes + (size_t)(in >> 3) * (KB * 16) + blk * 16 + (in & 7) * 2;
           *reinterpret_cast<uint2v*>(p) = uint2v{(uint32_t)h0.x | ((uint32_t)h1.x << 16), (uint32_t)h2.x | ((uint32_t)h3.x << 16)};
           if ((tid & 7) == 0) xsum[b * KB + blk] = sum;
-          // the normalised row itself is an output of the step (last-layer hidden state before lm_head)
-          if (a.gain && a.xn_out && blockIdx.x == 0 && k < K)
-            *reinterpret_cast<float4v*>(a.xn_out + (int64_t)(a.xn_row_map ? a.xn_row_map[b0 + b] : b0 + b) * a.xn_ld + k) = v;
+          if (a.gain) gemv_store_xn(a, b0 + b, k, v, k < K);
         }
       }
     }
@@ -269,11 +220,10 @@ __global__ __launch_bounds__(512) void gemv_int4_kernel(GemvArgs a, int b0, int 
     for (int b = 0; b < NB; ++b) acc[r][b] = 0.f;
   for (int t = 0; t < items; ++t) {
     if (t + 1 < items) load_item(t + 1, wnxt, snxt);
-    const int ci = t % nchp, c = PAIR ? 2 * ci + half : ci;
-    const bool live = !PAIR || (unit + (t / nchp) * nunits < ngroups && c < nch);
+    const auto it = wk.item(t);
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
-      const int blk = live ? c * CHB + u * 64 + lane : KB;
+      const int blk = it.live ? it.c * CHB + u * 64 + lane : KB;
       if (blk < KB) {
         uint32_t pr[RW][16];  // packed bf16 pairs (136 + q, 136 + q)
 #pragma unroll
@@ -310,56 +260,7 @@ __global__ __launch_bounds__(512) void gemv_int4_kernel(GemvArgs a, int b0, int 
         }
       }
     }
-    if (ci == nchp - 1) {  // row group finished: reduce across the wave and store
-      const int n0 = (unit + (t / nchp) * nunits) * R;
-#pragma unroll
-      for (int r = 0; r < RW; ++r)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[r][b] = wave_sum(acc[r][b]);
-      if constexpr (PAIR) {
-        const int buf = (t / nchp) & 1;
-        if (half == 1 && lane == 0) {
-#pragma unroll
-          for (int r = 0; r < RW; ++r)
-#pragma unroll
-            for (int b = 0; b < NB; ++b) red2[buf][wave >> 1][r][b] = acc[r][b];
-        }
-        __syncthreads();
-        if (half == 0) {
-#pragma unroll
-          for (int r = 0; r < RW; ++r)
-#pragma unroll
-            for (int b = 0; b < NB; ++b) acc[r][b] += red2[buf][wave >> 1][r][b];
-        }
-      }
-      // every lane holds every reduced sum: lane i < R * NB finishes output (r, b) = (i / NB, i % NB)
-      if (lane < R * NB && half == 0) {
-        const int r = lane / NB, b = lane % NB, n = n0 + r;
-        float v = 0.f, v2 = 0.f;
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr)
-#pragma unroll
-          for (int bb = 0; bb < NB; ++bb)
-            if (lane == rr * NB + bb) {
-              v = acc[rr][bb];
-              v2 = DUAL ? acc[RW - 1][bb] : 0.f;
-            }
-        if (n < a.N && b < nb) {
-          if (a.bias) v += a.bias[n];
-          if (DUAL)
-            v = apply_act(v, ACT_SILU) * v2;
-          else
-            v = apply_act(v, a.act);
-          const int64_t o = (int64_t)(b0 + b) * a.ldy + n;
-          if (a.resid) v += a.resid[o];
-          a.y[o] = v;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < RW; ++r)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[r][b] = 0.f;
-    }
+    if (it.last) gemv_finish_group<NB, R, DUAL, false, PAIR>(a, acc, red2, it.g, it.pass, wk.half, lane, wave, b0, nb);
     if (t + 1 < items) {
 #pragma unroll
       for (int u = 0; u < UNR; ++u)
@@ -370,75 +271,18 @@ __global__ __launch_bounds__(512) void gemv_int4_kernel(GemvArgs a, int b0, int 
         }
     }
   }
-  if (a.stamp.base && lane == 0) {
-    atomicMin(&st_t[0], t_begin);
-    atomicMax(&st_t[1], (unsigned long long)wall_clock64());
-    if (atomicAdd(&st_cnt, 1u) == 7u) {
-      const int e = *a.stamp.epoch;
-      if (e < a.stamp.max_epoch) {
-        unsigned long long* p = a.stamp.base + (size_t)e * a.stamp.stride + (size_t)blockIdx.x * 2;
-        p[0] = st_t[0];
-        p[1] = st_t[1];
-      }
-    }
-  }
-}
-
-// the measurement knobs of gemv.hip (read once; never set in production)
-static bool i4_pair_knob() {
-  static const bool p = !(getenv("ANYREF_GEMV_PAIR") && atoi(getenv("ANYREF_GEMV_PAIR")) == 0);
-  return p;
-}
-static int i4_grid_knob() {
-  static const int g = getenv("ANYREF_GEMV_GRID") ? atoi(getenv("ANYREF_GEMV_GRID")) : 0;
-  return g;
+  gemv_stamp_end(a.stamp, st_t, st_cnt, t_begin, lane);
 }
 
 template <int NB>
-static void gemv_int4_dispatch(const GemvArgs& a_in, int b0, int nb, hipStream_t s) {
-  GemvArgs a = a_in;
+static void gemv_int4_dispatch(const GemvArgs& a, int b0, int nb, hipStream_t s) {
   const int KB = cdiv(a.K, I4_BLOCK), G = cdiv(a.K, I4_GROUP);
   const size_t lds = (size_t)NB * KB * (64 + 4);
-  if (lds > 150 * 1024) throw std::runtime_error("gemv_int4: K too large for the LDS activation stage");
-  int grid = 256 * (lds > 76 * 1024 ? 1 : 2);
-  const int grid_rule = grid;
-  if (a.grid > 0 && a.grid < grid) grid = a.grid;
-  if (i4_grid_knob() > 0) grid = i4_grid_knob();
-  auto go = [&](auto xpt_tag) {
-    constexpr int XPT = decltype(xpt_tag)::value;
-    // algorithmic bytes: every nibble and every scale once (+ the tiny activation / output vectors)
-    const double wbytes = (double)a.N * ((double)a.K * 0.5 + G * 2.0) * (a.W2 ? 2 : 1) + (double)nb * (a.K + a.N) * 4;
-    char tag[40];
-    snprintf(tag, sizeof(tag), "gemv_int4w%s_x%d", a.W2 ? "_swiglu" : "", XPT);
-    ProfScope prof(tag, 2.0 * nb * a.N * (double)a.K * (a.W2 ? 2 : 1), wbytes, s);
-    if (g_stamp && g_stamp->on) a.stamp = g_stamp->slot(tag, wbytes, grid);
-    auto launch = [&](auto dual_t, auto pair_t) {
-      constexpr bool DUAL = decltype(dual_t)::value, PAIR = decltype(pair_t)::value;
-      auto kern = &gemv_int4_kernel<NB, DUAL, XPT, PAIR>;
-      static KernelAttrOnce once;  // per instantiation, per device
-      ensure_dyn_lds(once, reinterpret_cast<const void*>(kern), 150 * 1024);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, b0, nb);
-    };
-    using TT = std::true_type;
-    using FF = std::false_type;
-    // wave pairs where single waves would leave half of the grid without a row group (the rule of gemv_dispatch)
-    const bool pair = i4_pair_knob() && cdiv(a.N, a.W2 ? 1 : 2) * 2 <= (i4_grid_knob() > 0 ? grid : grid_rule) * 8;
-    if (a.W2) {
-      if (pair) launch(TT(), TT());
-      else launch(TT(), FF());
-    } else {
-      if (pair) launch(FF(), TT());
-      else launch(FF(), FF());
-    }
-  };
-  if (a.K <= 512 * 8)
-    go(std::integral_constant<int, 8>());
-  else if (a.K <= 512 * 24)
-    go(std::integral_constant<int, 24>());
-  else if (a.K <= 512 * 32)
-    go(std::integral_constant<int, 32>());
-  else
-    throw std::runtime_error("gemv_int4: K > 16384 not supported");
+  // algorithmic bytes: every nibble and every scale once (+ the tiny activation / output vectors)
+  const double wbytes = (double)a.N * ((double)a.K * 0.5 + G * 2.0) * (a.W2 ? 2 : 1) + (double)nb * (a.K + a.N) * 4;
+  gemv_dispatch_pass("gemv_int4", "int4w", a, lds, wbytes, nb, s, [&](auto xpt_t, auto dual_t, auto pair_t, const GemvArgs& g, int grid) {
+    gemv_launch<&gemv_int4_kernel<NB, decltype(dual_t)::value, decltype(xpt_t)::value, decltype(pair_t)::value>>(grid, lds, s, g, b0, nb);
+  });
 }
 
 void launch_gemv_int4(const GemvArgs& a, hipStream_t s) {
@@ -450,16 +294,7 @@ void launch_gemv_int4(const GemvArgs& a, hipStream_t s) {
       (a.xn_out && (((uintptr_t)a.xn_out & 15) || a.xn_ld % 4)))
     throw std::runtime_error("gemv_int4: x / gain / xn_out rows must be 16-byte aligned");
   // up to four batch rows per pass (5 - 8 rows: two passes)
-  for (int b0 = 0; b0 < a.B;) {
-    const int left = a.B - b0, nb = left < 4 ? left : 4;
-    if (nb == 1)
-      gemv_int4_dispatch<1>(a, b0, nb, s);
-    else if (nb == 2)
-      gemv_int4_dispatch<2>(a, b0, nb, s);
-    else
-      gemv_int4_dispatch<4>(a, b0, nb, s);
-    b0 += nb;
-  }
+  gemv_passes<4>(0, a.B, [&](auto nb_t, int b0, int nb) { gemv_int4_dispatch<decltype(nb_t)::value>(a, b0, nb, s); });
 }
 
 }  // namespace anyref

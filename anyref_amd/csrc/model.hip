@@ -329,14 +329,14 @@ class Model : public ModelBase {
   // workgroups (one round on the free CUs) a co-running step takes 3.97 -> 3.85 ms (image 39.8 - 40.3 -> 39.5 - 40.1 on one
   // box; 384 with the wave-pair kernels unbalanced: 4.1); alone 512 stays better (2.77 vs 2.89 ms).  Same sums either way.
   int gemv_grid_ = 0;
-  void gemv_w(GemvArgs& g, const Lin<W>& l, int row0 = 0) const {
-    g.ldw = l.stride();
+  void gemv_w(GemvArgs& g, const Lin<W>& l, int row0 = 0, int rstride = 1) const {  // rstride 2: every second row (gate / up)
+    g.ldw = (l.w4 ? l.ld4 : l.stride()) * rstride;
+    g.ld_gscale = l.ng4 * rstride;
+    g.ws_stride = rstride;
     g.grid = gemv_grid_;
     if (l.w4) {
       g.W = l.w4 + (size_t)row0 * l.ld4;
       g.gscale = l.s4 + (size_t)row0 * l.ng4;
-      g.ldw = l.ld4;
-      g.ld_gscale = l.ng4;
       g.w_int4 = 1;
     } else if (l.w8) {
       g.W = l.w8 + (size_t)row0 * l.stride();
@@ -401,6 +401,14 @@ class Model : public ModelBase {
     HIP_TRY(hipMemset(l.w4, 0x88, (size_t)n * l.ld4));  // q = 0
     l.s4 = talloc<bf16>((size_t)n * l.ng4);
     return l;
+  }
+  enum class WFmt { kInt4, kFp8 };  // the weight-only formats of the LLaMA linears, behind one pair of calls
+  Lin<W> alloc_quant(WFmt f, int n, int k, const std::string& name) {
+    return f == WFmt::kInt4 ? alloc_int4(n, k, name) : alloc_fp8(n, k);
+  }
+  void pack_rows_quant(WFmt f, Lin<W>& l, int row0, const std::string& name, int rows, int cols, int rstride = 1) {
+    if (f == WFmt::kInt4) pack_rows_int4(l, row0, name, rows, cols, rstride);
+    else pack_rows_fp8(l, row0, name, rows, cols, rstride);
   }
   bool skinny_off_ = getenv("ANYREF_NO_SKINNY_GEMV") != nullptr;
   void gemmf(hipStream_t s, const float* A, int lda, const LinF& l, float* C, int ldc, int M, int act,
@@ -796,26 +804,18 @@ void Model<T, TS>::finalize() {
       L.in_norm = affine(lp + "input_layernorm", false);
       L.post_norm = affine(lp + "post_attention_layernorm", false);
       const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-      if (int4w_) {
-        L.qkv = alloc_int4(3 * H, H, lp + "self_attn.q_proj.weight");
-        for (int j = 0; j < 3; ++j) pack_rows_int4(L.qkv, j * H, lp + "self_attn." + names[j] + ".weight", H, H);
-        L.o = alloc_int4(H, H, lp + "self_attn.o_proj.weight");
-        pack_rows_int4(L.o, 0, lp + "self_attn.o_proj.weight", H, H);
-        L.gu = alloc_int4(2 * F, H, lp + "mlp.gate_proj.weight");  // rows interleaved: 2j = gate_j, 2j + 1 = up_j
-        pack_rows_int4(L.gu, 0, lp + "mlp.gate_proj.weight", F, H, 2);
-        pack_rows_int4(L.gu, 1, lp + "mlp.up_proj.weight", F, H, 2);
-        L.down = alloc_int4(H, F, lp + "mlp.down_proj.weight");
-        pack_rows_int4(L.down, 0, lp + "mlp.down_proj.weight", H, F);
-      } else if (fp8w_) {
-        L.qkv = alloc_fp8(3 * H, H);
-        for (int j = 0; j < 3; ++j) pack_rows_fp8(L.qkv, j * H, lp + "self_attn." + names[j] + ".weight", H, H);
-        L.o = alloc_fp8(H, H);
-        pack_rows_fp8(L.o, 0, lp + "self_attn.o_proj.weight", H, H);
-        L.gu = alloc_fp8(2 * F, H);  // rows interleaved: 2j = gate_j, 2j + 1 = up_j (SwiGLU in the GEMM epilogue)
-        pack_rows_fp8(L.gu, 0, lp + "mlp.gate_proj.weight", F, H, 2);
-        pack_rows_fp8(L.gu, 1, lp + "mlp.up_proj.weight", F, H, 2);
-        L.down = alloc_fp8(H, F);
-        pack_rows_fp8(L.down, 0, lp + "mlp.down_proj.weight", H, F);
+      if (int4w_ || fp8w_) {
+        const WFmt f = int4w_ ? WFmt::kInt4 : WFmt::kFp8;
+        L.qkv = alloc_quant(f, 3 * H, H, lp + "self_attn.q_proj.weight");
+        for (int j = 0; j < 3; ++j) pack_rows_quant(f, L.qkv, j * H, lp + "self_attn." + names[j] + ".weight", H, H);
+        L.o = alloc_quant(f, H, H, lp + "self_attn.o_proj.weight");
+        pack_rows_quant(f, L.o, 0, lp + "self_attn.o_proj.weight", H, H);
+        // rows interleaved: 2j = gate_j, 2j + 1 = up_j (SwiGLU in the GEMV / GEMM epilogue)
+        L.gu = alloc_quant(f, 2 * F, H, lp + "mlp.gate_proj.weight");
+        pack_rows_quant(f, L.gu, 0, lp + "mlp.gate_proj.weight", F, H, 2);
+        pack_rows_quant(f, L.gu, 1, lp + "mlp.up_proj.weight", F, H, 2);
+        L.down = alloc_quant(f, H, F, lp + "mlp.down_proj.weight");
+        pack_rows_quant(f, L.down, 0, lp + "mlp.down_proj.weight", H, F);
       } else {
         const int rp = kRowPadBytes / (int)sizeof(W), ldh = H + rp;
         L.qkv.n = 3 * H;
@@ -1473,7 +1473,7 @@ void Model<T, TS>::llm_decode_step(hipStream_t s, int B, bool keep_q) {
     o.x = d_att_; o.ldx = H; gemv_w(o, L.o); o.y = d_x_; o.resid = d_x_; o.ldy = H; o.B = B; o.N = H; o.K = H;
     launch_gemv<T>(o, s);
     GemvArgs m;
-    m.x = d_x_; m.ldx = H; m.gain = L.post_norm.g; m.eps = c.llm_rms_eps; gemv_w(m, L.gu, 0); gemv_w2(m, L.gu, 1); m.ldw = 2 * (L.gu.w4 ? L.gu.ld4 : L.gu.stride()); m.ld_gscale = 2 * L.gu.ng4; m.ws_stride = 2;
+    m.x = d_x_; m.ldx = H; m.gain = L.post_norm.g; m.eps = c.llm_rms_eps; gemv_w(m, L.gu, 0, 2); gemv_w2(m, L.gu, 1);
     m.y = d_act_; m.ldy = F; m.B = B; m.N = F; m.K = H;
     launch_gemv<T>(m, s);
     GemvArgs d;

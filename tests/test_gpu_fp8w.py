@@ -47,7 +47,8 @@ def test_quantiser_bit_exact(N, K):
                                               # 5 .. 8 rows: one pass on the 4 x 4 x 4 MFMA form (gemv_rows8_kernel, fp8 pairs widened
                                               # to packed bf16); K = 13824 / 11008: down_proj, two K halves inside the launch
                                               (8, 1000, 5120, False, True), (8, 688, 5120, True, True), (5, 100, 256, False, False),
-                                              (8, 5120, 13824, False, False), (6, 130, 11008, False, False)])
+                                              (8, 5120, 13824, False, False), (6, 130, 11008, False, False),
+                                              (2, 2052, 256, 1, 1)])  # SwiGLU pairs past the wave-pair rule
 def test_gemv_fp8_vs_torch(B, N, K, dual, norm):
     lib = _lib.load()
     g = torch.Generator().manual_seed(B * N + K)

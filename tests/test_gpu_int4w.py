@@ -70,7 +70,9 @@ def test_quantiser_bit_exact(N, K):
                                              (1, 64, 13824, 0, 1),
                                              (2, 130, 5120, 1, 1),
                                              (1, 4096, 4096, 0, 0),     # the wave-pair shape
-                                             (6, 100, 256, 0, 0)])      # two passes
+                                             (6, 100, 256, 0, 0),       # two passes
+                                             (2, 2052, 256, 1, 1),      # past the wave-pair rule: one wave per row group
+                                             (1, 4100, 256, 0, 1)])
 def test_gemv_int4(B, N, K, dual, norm):
     """Reference: float64 of bf16(x_norm) W'^T.  Bound, from gemv_int4_kernel as written (the biased-nibble form):
     a lane takes whole 32-weight blocks.  Per block and batch row it forms  t = -136 xsum + sum_k (136 + q_k) x_k  and adds

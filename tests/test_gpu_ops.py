@@ -217,7 +217,8 @@ def test_gemm_a_row_gather(lib, ty, M, Msrc, N, K, c_f32):
                                              (8, 5120, 13824, 0, 0), (6, 33, 5120, 1, 1),
                                              # both sides of the two-K-half split at K = 13824, N off the row groups
                                              (5, 5123, 13824, 0, 1), (6, 77, 13824, 1, 0), (7, 4099, 13824, 0, 1),
-                                             (8, 5121, 13824, 0, 0), (8, 130, 13824, 1, 1)])
+                                             (8, 5121, 13824, 0, 0), (8, 130, 13824, 1, 1),
+                                             (2, 2052, 256, 1, 1)])           # SwiGLU pairs past the wave-pair rule
 def test_gemv(lib, ty, B, N, K, dual, norm):
     g = torch.Generator().manual_seed(B + N + K)
     x = torch.randn(B, K, generator=g)

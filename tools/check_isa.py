@@ -30,14 +30,14 @@ def asm_of(src, strict):
 def main():
     bad = 0
     allowed_scratch = ()
-    for src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemm_sp16h.hip", "gemv.hip", "attention.hip", "ops.hip"):
-        s = asm_of(src, strict=src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemm_sp16h.hip", "gemv.hip"))
+    for src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemm_sp16h.hip", "gemv.hip", "gemv_int4.hip", "attention.hip", "ops.hip"):
+        s = asm_of(src, strict=src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemm_sp16h.hip", "gemv.hip", "gemv_int4.hip"))
         for name, seg in re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", s):
             if int(seg) > 0 and not any(a in name for a in allowed_scratch):
                 print(f"FAIL {src}: {name} uses {seg} bytes of scratch")
                 bad += 1
         if src in ("gemm.hip", "gemm_f16.hip", "gemm_sp16.hip", "gemm_sp16h.hip"):
-            for m in re.finditer(r"^(_ZN6anyref16gemm_glds_kernel\S*):\n(.*?)\.Lfunc_end", s, re.S | re.M):
+            for m in re.finditer(r"^(_ZN6anyref16gemm_glds_kernel\S*):[^\n]*\n(.*?)\.Lfunc_end", s, re.S | re.M):
                 lines = m.group(2).split("\n")
                 n = sum(1 for k, l in enumerate(lines)
                         if "s_waitcnt vmcnt(0)" in l and any("ds_read" in x for x in lines[k + 1:k + 4]))
@@ -45,7 +45,7 @@ def main():
                     print(f"FAIL {src}: {m.group(1)} waits vmcnt(0) before {n} ds_read group(s)")
                     bad += 1
         if src == "gemm_sp16h.hip":
-            kernels = re.findall(r"^(_ZN6anyref16gemm_glds_kernel\S*):\n(.*?)\.Lfunc_end", s, re.S | re.M)
+            kernels = re.findall(r"^(_ZN6anyref16gemm_glds_kernel\S*):[^\n]*\n(.*?)\.Lfunc_end", s, re.S | re.M)
             if not kernels:
                 print("FAIL gemm_sp16h.hip: no LDS-DMA GEMM instantiation found")
                 bad += 1
