@@ -123,6 +123,7 @@ SYMBOLS = {
     "anyref_op_gemv_fp8": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     "anyref_op_quant_int4": (_I, [_P, _P, _I, _I, _P, _P]),
     "anyref_op_dequant_int4": (_I, [_P, _P, _P, _I, _I, _P]),
+    "anyref_op_gemm_int4": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "anyref_op_gemv_int4": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     "anyref_op_iou_counts": (_I, [_P, _P, _P, _I, _L, _P]),
     "anyref_op_avs_counts": (_I, [_P, _P, _P, _I, _L, _P, _I, _F, _P, _P]),

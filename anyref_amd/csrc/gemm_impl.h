@@ -444,11 +444,41 @@ __device__ __forceinline__ short8 fp8x8_to_bf16x8(uint2v r) {
   return o;
 }
 
+// W4: the weight operand is int4 group-quantised nibbles (ANYREF_MODE_PERF_INT4W; format: gemv_int4.hip).  BK = 64 is half
+// a scale group: a W tile row is 32 bytes (two 16-byte blocks of one group), DMA'd as stored, 32 rows per wave instruction;
+// block b of row r sits at block b ^ ((r >> 2) & 1).  Lane (i, g) of a fragment reads ONE dword (k = 32 ks + 8 g .. + 7):
+// ds_read_b32 is served in two groups of 32 lanes over 32 banks, the 32 lanes (16 rows x g in {0, 1}) touch only dwords 0 / 1
+// of a block, i.e. 16 of the 32 banks -- 2-way at best; rows 32 bytes apart repeat their banks every 4 rows, and the swizzle
+// on row bit 2 is what keeps it at 2-way (4-way without).  That is 4 LDS cycles per fragment, what the 16-byte read of a
+// bf16 fragment costs.  The tile's group scales (bf16 [N, ceil(K / 128)]) ride on the stage's DMA: every wave fetches, 4 bytes
+// per lane, the aligned dword that holds the scale of tile row 64 wave + lane at group (k0 + 64 t) >> 7 -- one more DMA
+// instruction per lane and tile, counted in LPT -- into the stage's tail; the reader picks the half by the element's parity.
+// Widening: the even nibbles (dw & 0x0F0F0F0F) and the odd ones ((dw >> 4) & 0x0F0F0F0F) sit one per byte, a byte goes to f32
+// in one instruction (v_cvt_f32_ubyteN), and fma(q + 8, s, -8 s) is exact (4 x 5 bits, then an exact cancellation): it equals
+// q * s with its low 16 bits zero, so v_cvt_pk_bf16_f32 (one per pair; nothing to round) gives the bf16 q * s, bit for bit what
+// dequant_int4_rows_kernel writes (q = 0 gives +0 in both).  Nibble n of the dword is weight 2 n (n < 4) or 2 (n - 4) + 1:
+// byte b of the even set is weight {0, 4, 1, 5}[b], of the odd set {2, 6, 3, 7}[b].  19 VALU per fragment (the route through
+// the GEMV's packed pairs (136 + q) took 33 and left the 320 x 96 tile VALU-bound at 1.6x its MFMA time).
+__device__ __forceinline__ short8 int4x8_to_bf16x8(uint32_t dw, float s, float neg8s) {
+  uint32_t ev = dw & 0x0F0F0F0Fu, od = (dw >> 4) & 0x0F0F0F0Fu;
+  // (opaque to the optimiser: it would otherwise fold the masks into a bit-field extract per nibble in front of every convert)
+  asm("" : "+v"(ev), "+v"(od));
+  const float2v s2{s, s}, n2{neg8s, neg8s};
+  auto pair = [&](uint32_t set, int b) {  // bytes b and b + 2 of the set: weights (2 j, 2 j + 1)
+    const float2v v = __builtin_elementwise_fma(float2v{(float)((set >> (8 * b)) & 0xFFu), (float)((set >> (8 * b + 16)) & 0xFFu)}, s2, n2);
+    uint32_t r;  // both values are bf16s already: the conversion rounds nothing (no builtin for it on gfx950)
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(v[0]), "v"(v[1]));
+    return r;
+  };
+  const uint4v o{pair(ev, 0), pair(od, 0), pair(ev, 1), pair(od, 1)};
+  return __builtin_bit_cast(short8, o);
+}
+
 // PERSIST: the grid is CAPPED (GemmArgs::max_wg workgroups, a multiple of 8) and every workgroup walks the tiles
 // id, id + gridDim.x, ... one after the other -- the SAM encoder's launches on the side stream, which must leave
 // CUs to the decode GEMVs of the main stream (DESIGN.md "CU share of the side stream").  A separate instantiation:
 // the one-tile-per-workgroup kernels are untouched.
-template <int BM, int BN, int WM, int WN, int NS, bool W8 = false, bool PERSIST = false, typename TT = bf16>
+template <int BM, int BN, int WM, int WN, int NS, bool W8 = false, bool PERSIST = false, typename TT = bf16, bool W4 = false>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
   using T = TT;  // bf16 or f16 (same tile, DMA and fragment code; the MFMA and the epilogue rounding differ)
   // sp16 (split-pair activations, common.h): the A rows are 2K/64 bf16 tiles [hi | lo] per 64 logical columns, walked
@@ -458,16 +488,18 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
   using ET = typename split_term<TT>::type;  // (sp16: bf16, sp16h: f16)
   constexpr int AX = SPLIT ? 2 : 1;  // 16-bit elements per logical A element
   static_assert(!W8 || !(is_half16<T>::value || SPLIT), "fp8 weights are widened to bf16");
+  static_assert(!W4 || !(is_half16<T>::value || SPLIT || W8 || PERSIST), "int4 weights are widened to bf16");
   constexpr int BK = 64, NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 16, NI = TN / 16;
   constexpr int ROWB = BK * 2;             // bytes per A tile row
-  constexpr int WROWB = W8 ? BK : BK * 2;  // bytes per W tile row
-  constexpr int WRPI = W8 ? 16 : 8;        // W rows per wave DMA instruction
-  constexpr int TILEB = BM * ROWB + BN * WROWB;  // one stage
+  constexpr int WROWB = W4 ? BK / 2 : W8 ? BK : BK * 2;  // bytes per W tile row
+  constexpr int WRPI = W4 ? 32 : W8 ? 16 : 8;            // W rows per wave DMA instruction
+  constexpr int SCB = W4 ? NW * 256 : 0;                 // W4: the tile's group scales, one dword per tile row (64 per wave)
+  constexpr int TILEB = BM * ROWB + BN * WROWB + SCB;    // one stage
   // LDS-DMA rounds: RA / RWF full rounds of all NW waves; a BN that is not a multiple of NW * WRPI rows adds a
   // last round that only waves 0 .. PW-1 take part in (128 x 160: 256 equal tiles for SAM fc2, 4096 x 1280)
   constexpr int RA = BM / (NW * 8), RWF = BN / (NW * WRPI), PW = (BN % (NW * WRPI)) / WRPI, RW = RWF + (PW > 0);
-  constexpr int LPT = RA + RWF;                          // DMA instructions per lane per tile (+1 on waves < PW)
+  constexpr int LPT = RA + RWF + (W4 ? 1 : 0);           // DMA instructions per lane per tile (+1 on waves < PW)
   // 16-bit weights: the wave's W fragments come in PAIRS with interleaved rows (see frag_col above: lane i = 4 g' + r' of
   // fragment 2p + q reads tile row 32 p + 8 g' + 4 q + r'), so the epilogue holds 8 consecutive columns per lane.  The W
   // tile's chunk swizzle is keyed on the row bits that differ among those 16 rows (bit 1 and bits 3-4; rows 2k, 2k + 1
@@ -478,10 +510,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
 #else
   // (not the 128 x 160 tile -- SAM fc2, f32 output: nothing to gain from 16-byte stores and its odd fifth fragment's
   //  2-way conflicts cost 1.3 us of 61.6; on one box, unpaired -> paired: qkv 45.3 -> 41.6 us, fc1 62.6 -> 59.8, proj 20.8 -> 20.0)
-  constexpr bool PAIRW = !W8 && !(NI % 2 == 1 && BM < 256);
+  constexpr bool PAIRW = !W8 && !W4 && !(NI % 2 == 1 && BM < 256);
 #endif
   constexpr int NIP = PAIRW ? (NI & ~1) : 0;  // fragments that come in pairs
   static_assert(BM % (NW * 8) == 0 && BN % WRPI == 0 && (PW == 0 || !W8), "tile rows must split over the waves");
+  static_assert(!W4 || BN <= NW * 64, "one scale DMA per wave and tile covers the tile's rows");
   static_assert(NS >= 2 && NS <= 4 && (NS - 2) * (LPT + 1) <= 63, "stage count / vmcnt range");
   extern __shared__ __attribute__((aligned(1024))) char smem[];  // the ONLY LDS object (rule: one array)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -517,7 +550,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
   const int m0 = tm * BM, n0 = tn * BN;
   const int z = blockIdx.z;
   const ET* __restrict__ A = reinterpret_cast<const ET*>(a.A) + (int64_t)z * a.sA * AX;
-  using WT = std::conditional_t<W8, uint8_t, ET>;
+  using WT = std::conditional_t<W8 || W4, uint8_t, ET>;
   const WT* __restrict__ W = reinterpret_cast<const WT*>(a.W) + (int64_t)z * a.sW;
 
   float4v acc[MI][NI];
@@ -540,7 +573,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
   }
 #pragma unroll
   for (int r = 0; r < RW; ++r) {
-    if constexpr (W8) {
+    if constexpr (W4) {
+      const int row = (r * NW + wave) * 32 + (lane >> 1);
+      int gn = n0 + row;
+      gn = gn < a.N ? gn : a.N - 1;
+      wsrc[r] = W + (int64_t)gn * a.ldw + (((lane & 1) ^ ((row >> 2) & 1)) << 4);
+    } else if constexpr (W8) {
       const int row = (r * NW + wave) * 16 + (lane >> 2);
       int gn = n0 + row;
       gn = gn < a.N ? gn : a.N - 1;
@@ -550,6 +588,23 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
       int gn = n0 + row;
       gn = gn < a.N ? gn : a.N - 1;
       wsrc[r] = W + (int64_t)gn * a.ldw + ((sp ^ wswz(row)) << 3);
+    }
+  }
+  // W4: element index (in bf16 scales) of this lane's tile row at group 0, the K slice's first 64-k tile, and -- per fragment
+  // of the wave, bit j -- the parity of the reading lane's row start (which half of the fetched dword holds its scale)
+  const uint32_t* __restrict__ S4 = reinterpret_cast<const uint32_t*>(a.gscale);
+  int se0 = 0, kt0 = 0;
+  uint32_t spar = 0;
+  if constexpr (W4) {
+    int gn = n0 + wave * 64 + lane;
+    gn = gn < a.N ? gn : a.N - 1;
+    se0 = gn * a.ld_gscale;
+    kt0 = (int)((int64_t)z * a.sA) >> 6;
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      int rn = n0 + wrow(j);
+      rn = rn < a.N ? rn : a.N - 1;
+      spar |= (uint32_t)((rn * a.ld_gscale) & 1) << j;
     }
   }
   // The stage index is a compile-time constant (loop unrolled by two below): with a runtime index hipcc
@@ -565,8 +620,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
 #pragma unroll
     for (int r = 0; r < RW; ++r)
       if (r < RWF || wave < PW)  // (wave-uniform)
-        __builtin_amdgcn_global_load_lds((gas_ptr)(wsrc[r] + (SPLIT ? t >> 1 : t) * BK),
+        __builtin_amdgcn_global_load_lds((gas_ptr)(wsrc[r] + (SPLIT ? t >> 1 : t) * (W4 ? BK / 2 : BK)),
                                          (las_ptr)(base + BM * ROWB + (r * NW + wave) * WRPI * WROWB), 16, 0, 0);
+    if constexpr (W4)  // the aligned dword that holds scale element se0 + group
+      __builtin_amdgcn_global_load_lds((gas_ptr)(S4 + ((se0 + ((kt0 + t) >> 1)) >> 1)),
+                                       (las_ptr)(base + BM * ROWB + BN * WROWB + wave * 256), 4, 0, 0);
   };
   // wait until at most N tiles' worth of this wave's own DMAs are still in flight
   auto wait_tiles = [&](auto n_c) {
@@ -583,7 +641,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
   // over), the fragments of phase p + 1 requested before the MFMAs of phase p, s_setprio 1 around every MFMA cluster
   // (guide T5: keeps hipcc from drifting the MFMAs in among the LDS reads).  Lab (scratch/lab/gemm8_lab.hip,
   // interleaved rounds): SAM qkv 44.4 -> 41.5 us, fc1-shaped 77 -> 73, 4096^3 +4 %, 8192^3 +3 %.
-  constexpr bool QUAD = BM == 256 && WM == 2 && !W8 && MI == 8 && NI == 4;  // (256 x 320: 104 fragment + 160 accumulator registers would spill)
+  constexpr bool QUAD = BM == 256 && WM == 2 && !W8 && !W4 && MI == 8 && NI == 4;  // (256 x 320: 104 fragment + 160 accumulator registers would spill)
   auto compute_quad = [&](auto buf_c) {
     constexpr int buf = decltype(buf_c)::value;
     constexpr int MH = MI / 2, NH0 = NI / 2, NH1 = NI - NH0;
@@ -641,7 +699,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
     mma(I1(), I1(), a1, b1);
     mma(I1(), I0(), a1, b0);
   };
-  auto compute = [&](auto buf_c) {
+  auto compute = [&](auto buf_c, int t) {
     if constexpr (QUAD) {
       compute_quad(buf_c);
       return;
@@ -649,6 +707,16 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
     constexpr int buf = decltype(buf_c)::value;
     const char* Ab = smem + buf * TILEB;
     const char* Wb = Ab + BM * ROWB;
+    float sf[W4 ? NI : 1], nsf[W4 ? NI : 1];  // W4: the group scale of each fragment's row, and -8 s
+    if constexpr (W4) {
+      const uint32_t gpar = (uint32_t)((kt0 + t) >> 1);
+#pragma unroll
+      for (int j = 0; j < NI; ++j) {
+        const uint32_t dw = *reinterpret_cast<const uint32_t*>(Wb + BN * WROWB + wrow(j) * 4);
+        sf[j] = __builtin_bit_cast(float, ((spar >> j) ^ gpar) & 1u ? dw & 0xFFFF0000u : dw << 16);
+        nsf[j] = -8.f * sf[j];
+      }
+    }
 #pragma unroll
     for (int ks = 0; ks < BK / 32; ++ks) {
       short8 af[MI], bfr[NI];
@@ -661,7 +729,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         const int row = wrow(j);
-        if constexpr (W8) {
+        if constexpr (W4) {
+          // k = 32 ks + 8 g .. + 7: dword g of block ks of the 32-byte row
+          const int g = lane >> 4;
+          bfr[j] = int4x8_to_bf16x8(
+              *reinterpret_cast<const uint32_t*>(Wb + row * WROWB + ((ks ^ ((row >> 2) & 1)) << 4) + (g << 2)), sf[j], nsf[j]);
+        } else if constexpr (W8) {
           // k = 32 ks + 8 g .. + 7: the 8 bytes at chunk (2 ks + g / 2), half (g & 1) of the 64-byte row
           const int g = lane >> 4, c8 = ks * 2 + (g >> 1);
           bfr[j] = fp8x8_to_bf16x8(
@@ -693,7 +766,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs a) {
         else wait_tiles(std::integral_constant<int, 0>());
         __builtin_amdgcn_s_barrier();  // ... and so have everyone else's; all waves are done with tile t-1
         if (t + NS - 1 < nt) stage(std::integral_constant<int, (B + NS - 1) % NS>(), t + NS - 1);  // into t-1's buffer
-        compute(b);
+        compute(b, t);
       }
     });
   }
@@ -874,13 +947,13 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   constexpr bool SP = is_split<T>::value;         // split-pair A (and C unless c_f32), bf16 W
   constexpr bool IS16 = sizeof(T) == 2 || SP;     // the 16-bit MFMA paths
   if constexpr (SP) {
-    if (a.K % 64 || a.lda % 64 || a.sA % 64 || a.w_fp8 || (!a.c_f32 && !a.slabs_out && (a.ldc % 64 || a.sC % 64)) ||
+    if (a.K % 64 || a.lda % 64 || a.sA % 64 || a.w_fp8 || a.w_int4 || (!a.c_f32 && !a.slabs_out && (a.ldc % 64 || a.sC % 64)) ||
         (a.norm_out && a.norm_ld % 64))
       throw std::runtime_error("gemm<sp16 / sp16h>: K, lda, the A batch stride (and ldc of a split-pair output) must be multiples of 64");
   }
   if (a.slabs_out && a.slabs > 1) {  // raw split-K: the consumer sums the slices
     if (!IS16 || a.batch != 1 || a.row_map || a.bias || a.resid || a.act != ACT_NONE || a.swiglu_pairs || a.w_fp8 ||
-        a.K % (64 * a.slabs))
+        a.w_int4 || a.K % (64 * a.slabs))
       throw std::runtime_error("gemm: raw split-K slabs take a plain bf16 product with K % (64 * slabs) == 0");
     GemmArgs g = a;
     g.K = a.K / a.slabs;
@@ -891,6 +964,19 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
     g.slabs_out = nullptr; g.slabs = 0; g.norm_out = nullptr;
     launch_gemm<T>(g, s);
     return;
+  }
+  if (a.w_int4) {  // what the int4 form cannot take is an error, never another route
+    if (sizeof(T) != 2 || is_half16<T>::value || SP || a.K % 64 || knobs().no_glds || knobs().tile >= 0 || knobs().ns320 == 2)
+      throw std::runtime_error("gemm: an int4 weight operand needs the bf16 LDS-DMA kernel (bf16 activations, K % 64 == 0, no forced tile or stage count)");
+    // the scale DMA fetches the aligned dword around a bf16 scale: an odd element count would put the last one's dword 2 bytes past the end
+    if (((int64_t)a.N * a.ld_gscale) & 1)
+      throw std::runtime_error("gemm: int4 weight operand: N * ld_gscale must be even (the scales are fetched as aligned dwords)");
+    if (!a.gscale || ((uintptr_t)a.gscale & 3) || ((uintptr_t)a.W & 15) || a.ldw % 16 || a.ldw * 2 < a.K || a.w_fp8 || a.col_scale ||
+        a.a_row_map)
+      throw std::runtime_error("gemm: int4 weight operand: 16-byte aligned nibble rows (ldw in bytes), 4-byte aligned group scales, no fp8 / column scale / gather");
+    if (a.batch != 1 && (a.sA % 64 || a.sW * 2 != a.sA))
+      throw std::runtime_error("gemm: int4 weight operand: batches are K slices (sA % 64 == 0, sW == sA / 2 bytes)");
+    if (a.batch == 1 && a.ld_gscale < cdiv(a.K, 128)) throw std::runtime_error("gemm: int4 weight operand: ld_gscale < ceil(K / 128)");
   }
   // ---- split-K decision: few 64x64 tiles, deep K, plain row-major output ----
   // (K >= 1024 when a norm rides on the reduction: CLIP out_proj, 24 tiles of 16 K steps + a LayerNorm launch otherwise)
@@ -908,7 +994,7 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
       g.K = a.K / splits;
       g.batch = splits;
       g.sA = g.K;   // column offset inside the same rows
-      g.sW = g.K;
+      g.sW = a.w_int4 ? g.K / 2 : g.K;  // (int4: bytes of nibble row; the scale index follows from z * sA in the kernel)
       g.C = ws; g.ldc = a.N; g.sC = slab; g.c_f32 = 1;
       g.bias = nullptr; g.resid = nullptr; g.act = ACT_NONE; g.alpha = 1.f; g.col_scale = nullptr; g.swiglu_pairs = 0;
       launch_gemm<T>(g, s);
@@ -949,7 +1035,7 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   if (a.a_row_map && (!IS16 || a.K % 64 || knobs().no_glds || knobs().tile >= 0 || a.batch != 1))
     throw std::runtime_error("gemm: a_row_map is taken by the 16-bit LDS-DMA kernel only (K % 64 == 0, batch 1)");
   if (a.K % VEC || a.lda % VEC || a.ldw % VEC || ((uintptr_t)a.A & 15) || ((uintptr_t)a.W & 15) ||
-      (a.sA % VEC) || (a.sW % VEC))
+      (a.sA % VEC) || (a.sW % (a.w_int4 ? 16 : VEC)))
     throw std::runtime_error("gemm: K/lda/ldw must be multiples of 16 bytes and operands 16-byte aligned");
   // Tile choice, from measurements on MI355X (scratch/bench_gemm.py, all four variants per shape):
   // 128x128 once there are >= 2 tiles per CU; 64x128 for mid-size N (more, smaller tiles fill the
@@ -985,7 +1071,8 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   }
   const double flops = 2.0 * a.M * a.N * (double)a.K * a.batch;
   // algorithmic bytes: A (pairs: 4 bytes per element), W as stored (fp8: 1 byte, pairs mode: bf16), C
-  const double wbytes = a.w_fp8 ? 1.0 : (SP ? 2.0 : (double)sizeof(T));
+  // (int4: nibbles + one bf16 scale per 128 k)
+  const double wbytes = a.w_int4 ? 0.5 + 2.0 / 128 : a.w_fp8 ? 1.0 : (SP ? 2.0 : (double)sizeof(T));
   const double bytes = ((double)a.M * a.K * sizeof(T) + (double)a.N * a.K * wbytes) * a.batch +
                        (double)a.M * a.N * (a.c_f32 ? 4 : sizeof(T)) * a.batch;
   if (a.w_fp8 && (sizeof(T) != 2 || a.K % 64 || knobs().no_glds || knobs().tile >= 0))
@@ -1013,6 +1100,27 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
             hipLaunchKernelGGL(kern8, dim3(nwg8, 1, a.batch), dim3(WM * WN * 64), NS * ((size_t)BM * 128 + (size_t)BN * 64),
                                s, a);
             return;
+          }
+        }
+        if constexpr (std::is_same<T, bf16>::value) {
+          if (a.w_int4) {  // int4 weight operand: the tiles the LLM linears reach (prefill, M = B S, decode rows, split-K slabs)
+            if constexpr ((BM == 64 && BN == 256) || (BM == 128 && BN == 128) || (BM == 256 && BN == 256) ||
+                          (BM == 320 && (BN == 64 || BN == 96) && NS == 3)) {
+              auto kern4 = &gemm_glds_kernel<BM, BN, WM, WN, NS, false, false, bf16, true>;
+              constexpr size_t lds4 = NS * ((size_t)BM * 128 + (size_t)BN * 32 + (size_t)WM * WN * 256);
+              static KernelAttrOnce once4;
+              ensure_dyn_lds(once4, reinterpret_cast<const void*>(kern4), (int)lds4);
+              const int tiles_m4 = cdiv(a.M, BM), nwg4 = tiles_m4 * cdiv(a.N, BN);
+              int gm4 = (int)lround(sqrt((double)(nwg4 > 8 ? nwg4 / 8 : 1)));
+              a.group_m = gm4 < 1 ? 1 : (gm4 > tiles_m4 ? tiles_m4 : gm4);
+              char tag4[56];
+              snprintf(tag4, sizeof(tag4), "%s_int4w%s", tag, a.M <= 16 ? "_dec" : "");  // _dec: decode rows (weight streaming)
+              ProfScope prof(tag4, flops, bytes, s);
+              hipLaunchKernelGGL(kern4, dim3(nwg4, 1, a.batch), dim3(WM * WN * 64), lds4, s, a);
+              return;
+            } else {
+              throw std::runtime_error("gemm: no int4 form of this tile (unreachable)");
+            }
           }
         }
         auto kern = &gemm_glds_kernel<BM, BN, WM, WN, NS, false, false, T>;
@@ -1103,11 +1211,11 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
         go(I256(), I256(), I2(), I4(), I2(), "gemm_bf16_256x256");
         return;
       }
-      if (!a.w_fp8 && a.M >= 1024 && a.N % 320 == 0 && fill320 >= 0.95) {
+      if (!a.w_fp8 && !a.w_int4 && a.M >= 1024 && a.N % 320 == 0 && fill320 >= 0.95) {
         go(I256(), I320(), I2(), I4(), I2(), "gemm_bf16_256x320");  // SAM fc1: 16 x 16 tiles = one per CU
         return;
       }
-      if (!a.w_fp8 && a.M >= 1024 && a.N % 160 == 0 && fill160 >= 0.95 && fill128 < 0.7) {
+      if (!a.w_fp8 && !a.w_int4 && a.M >= 1024 && a.N % 160 == 0 && fill160 >= 0.95 && fill128 < 0.7) {
         go(I128(), I160(), I4(), I2(), I3(), "gemm_bf16_128x160s3");  // SAM fc2: 32 x 8 tiles = one per CU
         return;
       }
@@ -1156,7 +1264,7 @@ void launch_gemm(const GemmArgs& a_in, hipStream_t s) {
         // CLIP qkv / fc1 (257 x 3072 / 4096 x 1024): 72 / 96 workgroups of 128^2 stream 32 KB per K tile each through L2 -> LDS
         // (~0.5 us x 16 K tiles + ~4 us of launch, first tile and epilogue); 64 x 128 tiles are 120 / 160 workgroups at 24 KB
         static const bool clip64 = !(getenv("ANYREF_GEMM_CLIP64") && atoi(getenv("ANYREF_GEMM_CLIP64")) == 0);
-        if (clip64 && !a.w_fp8 && a.batch == 1 && a.M > 128 && a.M <= 320 && a.N >= 2048 && a.N < 8192 && a.K <= 2048 && t128 <= cus) {
+        if (clip64 && !a.w_fp8 && !a.w_int4 && a.batch == 1 && a.M > 128 && a.M <= 320 && a.N >= 2048 && a.N < 8192 && a.K <= 2048 && t128 <= cus) {
           go(I64(), I128(), I1(), I4(), I3(), "gemm_bf16_64x128s3");
           return;
         }

@@ -143,6 +143,14 @@ struct GemmArgs {
   // column n is multiplied by col_scale[n]
   int w_fp8 = 0;
   const float* col_scale = nullptr;
+  // int4 group-quantised weight operand (bf16 LDS-DMA kernel only; format: gemv_int4.hip): W holds nibble rows (ldw, sW in
+  // bytes), gscale bf16 [N, ceil(K / 128)] at row stride ld_gscale (elements).  The fragments are widened to the bf16 q * s
+  // in registers.  batch > 1 then means K slices of ONE product (the launcher's split-K): slice z covers k from z * sA, so
+  // sW * 2 == sA, a multiple of 64; the scale index comes from that absolute k.  N * ld_gscale must be even (the scales are
+  // fetched as aligned dwords).  As with w_fp8, max_wg and the ANYREF_GEMM_GM knob are not honoured.
+  int w_int4 = 0;
+  const void* gscale = nullptr;
+  int ld_gscale = 0;
   int group_m = 0;  // > 0 (set by the launcher): grouped tile order, this many tile rows per group
   // > 0: at most this many workgroups (bf16 LDS-DMA kernel, M >= 128-row tiles, batch 1); each walks several tiles
   int max_wg = 0;

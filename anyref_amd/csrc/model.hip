@@ -313,9 +313,13 @@ class Model : public ModelBase {
         }
       }
       if constexpr (std::is_same<T, bf16>::value) {
-        if (l.w4) {  // int4: multiply the (exact) bf16 image of q * s
-          launch_dequant_int4_rows(l.w4, l.ld4, l.s4, l.ng4, l.n, l.k, deq_buf_, l.k, s);
-          a.W = deq_buf_; a.ldw = l.k;
+        if (l.w4) {
+          if (l.k % 64 == 0) {  // nibbles straight into the GEMM (each fragment widened to the bf16 q * s in registers)
+            a.W = l.w4; a.ldw = l.ld4; a.w_int4 = 1; a.gscale = l.s4; a.ld_gscale = l.ng4;
+          } else {              // K % 64 != 0: multiply the (exact) bf16 image of q * s
+            launch_dequant_int4_rows(l.w4, l.ld4, l.s4, l.ng4, l.n, l.k, deq_buf_, l.k, s);
+            a.W = deq_buf_; a.ldw = l.k;
+          }
         }
       }
     }
@@ -360,7 +364,7 @@ class Model : public ModelBase {
   // dtype code of the embedding table (packed as W) for the embed / argmax kernels: 0 = f32, 1 = bf16, 2 = f16
   static constexpr int kEmbDtype = std::is_same<W, bf16>::value ? 1 : is_half16<W>::value ? 2 : 0;
   bool fp8w_ = false;
-  W* deq_buf_ = nullptr;  // bf16 image of the largest fp8 weight (prefill operand)
+  W* deq_buf_ = nullptr;  // bf16 image of the largest fp8 / int4 weight whose K % 64 != 0 keeps it out of the quantised-operand GEMM
   // pack rows of a raw f32 tensor as fp8 + scales into l (rows [row0, row0 + rows))
   // rstride 2: every second row of l (gate / up interleave), starting at row0
   void pack_rows_fp8(Lin<W>& l, int row0, const std::string& name, int rows, int cols, int rstride = 1) {
@@ -857,8 +861,14 @@ void Model<T, TS>::finalize() {
       deq_buf_ = talloc<W>(big);
     } else {
       lm_head_ = pack_linear("lm_head.weight", "", V, H, 8, kRowPadBytes / (int)sizeof(W));
-      // int4: the bf16 image of the largest linear (prefill / teacher / MFMA-decode GEMM operand); lm_head stays bf16
-      if (int4w_) deq_buf_ = talloc<W>(std::max((size_t)2 * F * H, (size_t)3 * H * H));
+      // int4: lm_head stays bf16.  The GEMM multiplies the nibbles as stored; only a linear with K % 64 != 0 goes through a
+      // bf16 image, sized to the largest such linear (none at 7B / 13B widths: no buffer)
+      if (int4w_) {
+        size_t big = 0;
+        if (H % 64) big = std::max((size_t)2 * F * H, (size_t)3 * H * H);  // qkv, o, gate / up: K = H
+        if (F % 64) big = std::max(big, (size_t)H * F);                     // down: K = F
+        if (big) deq_buf_ = talloc<W>(big);
+      }
     }
     // rotary table, same fp32 op order as HF LlamaRotaryEmbedding
     std::vector<float> tab((size_t)S * hd);

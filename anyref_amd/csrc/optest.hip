@@ -476,6 +476,18 @@ int anyref_op_dequant_int4(void* stream, const uint8_t* q, const void* scale_bf1
   OP_GUARD(launch_dequant_int4_rows(q, (K + 127) / 128 * 64, scale_bf16, (K + 127) / 128, N, K, out_bf16, K, (hipStream_t)stream));
 }
 
+int anyref_op_gemm_int4(void* stream, const void* A, const uint8_t* W4, const void* scale_bf16, const float* bias, void* C,
+                        const float* resid, int M, int N, int K, int act, int c_f32, int swiglu) {
+  OP_GUARD({
+    TagScope tags((hipStream_t)stream);
+    GemmArgs a;
+    a.A = A; a.lda = K; a.W = W4; a.ldw = (K + 127) / 128 * 64; a.w_int4 = 1; a.gscale = scale_bf16; a.ld_gscale = (K + 127) / 128;
+    a.bias = bias; a.C = C; a.ldc = swiglu ? N / 2 : N; a.resid = resid; a.ldr = N; a.M = M; a.N = N; a.K = K; a.act = act;
+    a.c_f32 = c_f32; a.swiglu_pairs = swiglu ? 1 : 0;
+    launch_gemm<bf16>(a, (hipStream_t)stream);
+  });
+}
+
 int anyref_op_gemv_int4(void* stream, const float* x, const float* gain, float eps, const uint8_t* W, const uint8_t* W2,
                         const void* scale_bf16, const void* scale2_bf16, float* y, const float* resid, int B, int N, int K) {
   OP_GUARD({

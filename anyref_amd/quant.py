@@ -90,6 +90,22 @@ def dequantize_groups_int4(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     return q.to(torch.float32) * s.to(torch.float32).repeat_interleave(INT4_GROUP, dim=1)[:, :K]
 
 
+def pack_groups_int4(q: torch.Tensor) -> torch.Tensor:
+    """The reference statement of the device's nibble layout (what `quant_int4_rows_kernel` stores; the tests hold the device
+    bytes against it): q int8 [N, K] in -7 .. 7 -> nibble rows uint8 [N, ceil(K / 128) * 64] (positions past K: q = 0).
+
+    A nibble holds q + 8.  A dword is 8 consecutive weights: weight e sits at bit 4 * ((e >> 1) + 4 * (e & 1)), so that
+    ((dword >> 4 j) & 0x000F000F) | 0x43004300 is the packed bf16 pair (136 + q[2 j], 136 + q[2 j + 1]); dwords are
+    little-endian and in k order (a 16-byte block is 32 weights of one group)."""
+    N, K = q.shape
+    G = (K + INT4_GROUP - 1) // INT4_GROUP
+    qp = torch.zeros(N, G * INT4_GROUP, dtype=torch.int64)
+    qp[:, :K] = q
+    shift = torch.tensor([4 * ((e >> 1) + 4 * (e & 1)) for e in range(8)], dtype=torch.int64)
+    word = ((qp + 8).view(N, G * 16, 8) << shift).sum(-1)
+    return torch.stack([(word >> (8 * b)) & 255 for b in range(4)], -1).to(torch.uint8).view(N, G * 64)
+
+
 def is_int4_weight(name: str) -> bool:
     """The tensors ANYREF_MODE_PERF_INT4W holds in int4: q/k/v/o and gate/up/down of every layer (not lm_head)."""
     return _LLM_LINEAR_INT4.match(name) is not None

@@ -67,7 +67,9 @@ extern "C" {
  * consecutive k of an output row (weight-only, quantised at finalize; the last group of a row may be short).  Per group:
  * amax = max|w|; amax < 2^-100: s = 1, q = 0; else s = amax / 7 (f32) rounded UP to 5 significant bits (a bf16 with three zero
  * low mantissa bits, amax / 7 <= s <= 1.0625 amax / 7), q = clamp(rne(w / s), -7, 7), held value w' = q * s -- exactly a bf16,
- * so the decode GEMV (sum_g s_g sum_k q_k x_k) and the prefill GEMM (a bf16 image of w') multiply one set of weights.
+ * so the decode GEMV (sum_g s_g sum_k q_k x_k) and the MFMA GEMM of prefill, the teacher-forced forward, llm_forward and decode
+ * steps of more than 8 rows (it reads the nibbles as stored and widens each operand fragment to the bf16 w' in registers; a
+ * linear whose K is not a multiple of 64 goes through a bf16 image of w' instead) multiply one set of weights.
  * lm_head, the embeddings, the vision / audio towers, SAM and every activation stay as in PERF.  About 0.52 bytes per LLM
  * linear element instead of 2.  llm_dim and llm_mlp must be multiples of 16 (finalize fails, naming the tensor).
  * A byte / accuracy trade (relative rms weight error 0.12 - 0.15 on Gaussian weights), not a parity mode;

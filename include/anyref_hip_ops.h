@@ -74,6 +74,12 @@ int anyref_op_gemv_fp8(void* stream, const float* x, const float* gain, float ep
 int anyref_op_quant_int4(void* stream, const float* src, int N, int K, uint8_t* q, void* scale_bf16);
 /* q, scale as written by anyref_op_quant_int4 -> out bf16 [N,K] = q * scale (exact) */
 int anyref_op_dequant_int4(void* stream, const uint8_t* q, const void* scale_bf16, int N, int K, void* out_bf16);
+/* bf16 GEMM with an int4 weight operand (q, scale as written by anyref_op_quant_int4; K % 64 == 0, anything else is an error):
+ * C = act(A W'^T + bias) (+ resid), W' = q * scale; A bf16 [M,K]; C f32 or bf16 [M,N].  swiglu: the rows of W are interleaved
+ * (gate_j, up_j) pairs and C [M, N/2] = silu(c[m, 2j]) * c[m, 2j+1] (no bias / resid / act).  The launch tags are left in
+ * anyref_op_last_tags(). */
+int anyref_op_gemm_int4(void* stream, const void* A, const uint8_t* W4, const void* scale_bf16, const float* bias, void* C,
+                        const float* resid, int M, int N, int K, int act, int c_f32, int swiglu);
 /* decode GEMV on int4 weights: y[b,n] = sum_g scale[n,g] * sum_{k in g} bf16(norm(x))[b,k] * q[n,k] (SwiGLU pair if W2) (+ resid) */
 int anyref_op_gemv_int4(void* stream, const float* x, const float* gain, float eps, const uint8_t* W, const uint8_t* W2,
                         const void* scale_bf16, const void* scale2_bf16, float* y, const float* resid, int B, int N, int K);

@@ -4,7 +4,8 @@
   * no kernel may use scratch (private segment): a kernel with register spills returned wrong,
     run-to-run different results from a hipGraph replay / beside a second stream on this stack
     (DESIGN.md, "Compiler / runtime hazards")
-  * the LDS-DMA GEMM must not wait vmcnt(0) in front of a tile's first ds_read (Makefile note on gemm.o)
+  * the LDS-DMA GEMM (bf16, f16, pair, fp8- and int4-operand forms) must not wait vmcnt(0) in front of a tile's first
+    ds_read (Makefile note on gemm.o)
   * the f16 decode GEMV (ANYREF_MODE_PERF_F16) must multiply on the packed f16 dot (v_dot2[c]_f32_f16), not fall back to
     unpack + FMA
   * the f16-pair GEMM (ANYREF_MODE_PARITY16_F16) must multiply on the f16 MFMA only (a bf16 MFMA there would read f16 terms as
@@ -44,6 +45,10 @@ def main():
                 if n:
                     print(f"FAIL {src}: {m.group(1)} waits vmcnt(0) before {n} ds_read group(s)")
                     bad += 1
+        if src == "gemm.hip":  # the int4-operand form (last template argument) is among the kernels checked above
+            if not re.search(r"^_ZN6anyref16gemm_glds_kernelI\S*NS_4bf16ELb1EEEvNS_8GemmArgsE:", s, re.M):
+                print("FAIL gemm.hip: no int4-operand LDS-DMA GEMM instantiation found")
+                bad += 1
         if src == "gemm_sp16h.hip":
             kernels = re.findall(r"^(_ZN6anyref16gemm_glds_kernel\S*):[^\n]*\n(.*?)\.Lfunc_end", s, re.S | re.M)
             if not kernels:
