@@ -92,6 +92,9 @@ SYMBOLS = {
     "anyref_sam_encode": (_I, [_P, _P, _P, _I, _P]),
     "anyref_mask_decode": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "anyref_llm_forward": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "anyref_llm_extend": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "anyref_set_draft": (_I, [_P, _P, _P, _I, _I]),
+    "anyref_draft_stats": (_I, [_P, _P, _P, _I, _P, _P]),
     "anyref_project_audio": (_I, [_P, _P, _P, _I, _P]),
     "anyref_audio_encode": (_I, [_P, _P, _P, _I, _P]),
     "anyref_seg_tail": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _L, _P, _P]),
@@ -139,6 +142,7 @@ SYMBOLS = {
     "anyref_op_decode_attn": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _I]),
     "anyref_op_rope_cache": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "anyref_op_argmax": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "anyref_op_draft_accept": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_norm": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _F, _I]),
     "anyref_op_attention": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _I, _I]),
     "anyref_op_attention_tab": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _I, _I]),

@@ -110,6 +110,20 @@ int anyref_llm_forward(anyref_handle* h, void* stream, const float* embeds, cons
   GUARD(h, h->m->llm_forward((hipStream_t)stream, embeds, lens, B, S, hidden, logits, attn_q, attn_row));
 }
 
+int anyref_llm_extend(anyref_handle* h, void* stream, const float* embeds, const int32_t* pos0, const int32_t* lens, int B,
+                      int n, float* hidden, float* logits) {
+  GUARD(h, h->m->llm_extend((hipStream_t)stream, embeds, pos0, lens, B, n, hidden, logits));
+}
+
+int anyref_set_draft(anyref_handle* h, const int64_t* draft_ids, const int32_t* draft_lens, int B, int Kmax) {
+  GUARD(h, h->m->set_draft(draft_ids, draft_lens, B, Kmax));
+}
+
+int anyref_draft_stats(anyref_handle* h, int32_t* offered, int32_t* accepted, int B, int32_t* decode_steps,
+                       int32_t* verify_passes) {
+  GUARD(h, h->m->draft_stats(offered, accepted, B, decode_steps, verify_passes));
+}
+
 int anyref_audio_encode(anyref_handle* h, void* stream, const float* mel, int n, float* emb) {
   GUARD(h, h->m->audio_encode((hipStream_t)stream, mel, n, emb));
 }

@@ -410,6 +410,14 @@ void launch_argmax(const float* x, int M, int N, int ldx, int64_t* out, hipStrea
 // b * maxS + pos[b], kvlen[b] = pos[b] + 1; table dtype 0 = f32, 1 = bf16, 2 = f16
 void launch_argmax_next(const float* x, int M, int N, int ldx, int64_t* out, int* pos, const void* table, int dtype,
                         int D, int maxS, float* x_next, int* row_map, int* kvlen, hipStream_t s);
+// Accept step of the draft-verified greedy decode: logits f32 [B * k, N] (row stride ldx) of a verification pass that fed
+// draft i64 [B, k] (dlen[b] <= k valid ids per row) behind next[b].  p i64 [B * k] receives the row argmaxes; per row, with
+// g[0] = next[b] and g[j + 1] = p[j], accepted[b] = m = leading j < dlen[b] with g[j] == draft[j]; tokens i64 [B, k + 1] gets
+// g[0 .. m]; then the state launch_argmax_next leaves: next[b] = g[m], pos[b] += m, x_next[b] = table[g[m]], row_map, kvlen.
+// Two launches (argmax over B * k rows, one small workgroup per sequence); k <= 256.
+void launch_draft_accept(const float* logits, int B, int k, int N, int ldx, int64_t* p, const int64_t* draft, const int* dlen,
+                         int64_t* next, int* pos, int64_t* tokens, int* accepted, const void* table, int dtype, int D, int maxS,
+                         float* x_next, int* row_map, int* kvlen, hipStream_t s);
 // ConvTranspose2d k2s2 output un-shuffle (+ LayerNorm2d + GELU): tmp f32 [n*g*g, 4*C] (col = (dy*2+dx)*C+c)
 // -> out T [n*(2g)*(2g), C] NHWC
 template <typename T>

@@ -49,6 +49,8 @@ class ModelBase {
                            float* iou, const int32_t* resized_hw, const int32_t* orig_hw, float* out_masks) = 0;
   virtual void llm_forward(hipStream_t s, const float* embeds, const int32_t* lens, int B, int S, float* hidden,
                            float* logits, const int32_t* attn_q, float* attn_row) = 0;
+  virtual void llm_extend(hipStream_t s, const float* embeds, const int32_t* pos0, const int32_t* lens, int B, int n,
+                          float* hidden, float* logits) = 0;
   virtual void project_audio(hipStream_t s, const float* audio_emb, int n, float* out) = 0;
   virtual void audio_encode(hipStream_t s, const float* mel, int n, float* emb) = 0;
   virtual void seg_tail(hipStream_t s, const float* sam_images, const int64_t* ids, const int32_t* ids_lens,
@@ -76,6 +78,30 @@ class ModelBase {
   // the caller may produce them (ImageBind audio trunk + projector) on a stream of its own, beside the CLIP tower
   void set_extra_event(void* ev) { extra_ev_ = ev; }
   void* extra_ev_ = nullptr;
+  // proposed continuation for the NEXT generate (anyref_set_draft): one-shot, taken (and cleared) at its entry
+  static constexpr int kDraftCap = 64;  // tokens per row a verification pass is fed at most
+  void set_draft(const int64_t* ids, const int32_t* lens, int B, int Kmax) {
+    draft_ids_.clear();  // (a refused call leaves nothing armed either)
+    if (!ids || !lens) return;
+    if (B < 1 || B > cfg.max_batch || Kmax < 0) throw std::runtime_error("set_draft: bad batch / Kmax");
+    std::vector<std::vector<int64_t>> d(B);
+    for (int b = 0; b < B; ++b) {
+      if (lens[b] < 0 || lens[b] > Kmax) throw std::runtime_error("set_draft: draft_lens[b] outside [0, Kmax]");
+      d[b].assign(ids + (size_t)b * Kmax, ids + (size_t)b * Kmax + lens[b]);
+    }
+    draft_ids_.swap(d);
+  }
+  void draft_stats(int32_t* offered, int32_t* accepted, int B, int32_t* decode_steps, int32_t* verify_passes) const {
+    for (int b = 0; b < B; ++b) {
+      if (offered) offered[b] = b < (int)stat_offered_.size() ? stat_offered_[b] : 0;
+      if (accepted) accepted[b] = b < (int)stat_accepted_.size() ? stat_accepted_[b] : 0;
+    }
+    if (decode_steps) *decode_steps = stat_steps_;
+    if (verify_passes) *verify_passes = stat_passes_;
+  }
+  std::vector<std::vector<int64_t>> draft_ids_;  // per row; empty: nothing pending
+  std::vector<int> stat_offered_, stat_accepted_;  // of the last generate
+  int stat_steps_ = 0, stat_passes_ = 0;
   // hipGraph replay of the greedy decode step (default on)
   void set_graphs(bool on) { use_graphs_ = on; }
   // workgroup cap of the encoder's GEMM / attention launches while it co-runs with the decode loop (0 = uncapped)

@@ -211,6 +211,9 @@ class Model : public ModelBase {
     if (ev_sam_) (void)hipEventDestroy(ev_sam_);
     if (next_host_) (void)hipHostFree(next_host_);
     if (stage_) (void)hipHostFree(stage_);
+    if (ext_stage_) (void)hipHostFree(ext_stage_);
+    if (drf_host_) (void)hipHostFree(drf_host_);
+    if (ext_ev_) (void)hipEventDestroy(ext_ev_);
     for (auto e : ev_tok_)
       if (e) (void)hipEventDestroy(e);
     for (auto e : stage_ev_)
@@ -242,6 +245,8 @@ class Model : public ModelBase {
                    const int32_t* resized_hw, const int32_t* orig_hw, float* out_masks) override;
   void llm_forward(hipStream_t s, const float* embeds, const int32_t* lens, int B, int S, float* hidden,
                    float* logits, const int32_t* attn_q, float* attn_row) override;
+  void llm_extend(hipStream_t s, const float* embeds, const int32_t* pos0, const int32_t* lens, int B, int n, float* hidden,
+                  float* logits) override;
   void project_audio(hipStream_t s, const float* audio_emb, int n, float* out) override;
   void audio_encode(hipStream_t s, const float* mel, int n, float* emb) override;
   void seg_tail(hipStream_t s, const float* sam_images, const int64_t* ids, const int32_t* ids_lens,
@@ -441,8 +446,37 @@ class Model : public ModelBase {
 
   // ---- stages ----
   void clip_tower(hipStream_t s, const float* images, int B);  // -> img_feat_ [B,n,H]
-  void llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev, bool keep_q);
+  // ext (optional): the Sp rows of sequence b sit at cache positions ext->pos0[b] + i behind an existing KV cache (the
+  // "extend" form: anyref_llm_extend, the verification pass of a draft); null: a prompt from position 0, as ever
+  struct PrefillExt {
+    const int* pos0 = nullptr;     // dev [B] rows already cached
+    const int* lens = nullptr;     // dev [B] valid new rows (what the caller passes as lens_dev)
+    const int* kv_len = nullptr;   // dev [B] pos0[b] + lens[b]
+    const int* hid_rows = nullptr; // dev [B * Sp] row of hidden_all_ for pass row b * Sp + i, -1 for i >= lens[b]
+    int Sk = 0;                    // max_b kv_len[b]
+  };
+  void llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev, bool keep_q, const PrefillExt* ext = nullptr);
   void llm_decode_step(hipStream_t s, int B, bool keep_q);
+  // The extend form's index vectors and the draft verification's buffers, allocated at first use (a handle that never
+  // extends pays nothing).  ext_stage_ (pinned) is rewritten per pass behind ext_ev_, like the stage_ regions below.
+  //   ext_idx_: pos0 [MB] | lens [MB] | kv_len [MB] | hid_rows [MB * S]        (device i32; ext_stage_ mirrors it)
+  //   drf_ids_ [MB * kDraftCap] draft ids (padded with 0), drf_p_ the pass's argmaxes, drf_tok_ [MB * (kDraftCap + 1)] the
+  //   accepted tokens, drf_acc_ [MB] their count - 1; drf_host_ (pinned): ids | tokens | accepted
+  int* ext_idx_ = nullptr;
+  int* ext_stage_ = nullptr;
+  hipEvent_t ext_ev_ = nullptr;
+  bool ext_busy_ = false;
+  int64_t *drf_ids_ = nullptr, *drf_p_ = nullptr, *drf_tok_ = nullptr, *drf_host_ = nullptr;
+  int* drf_acc_ = nullptr;
+  float* drf_logits_ = nullptr;  // [MB * kDraftCap, vocab]
+  void ensure_ext();
+  void ensure_draft();
+  // upload pos0 / lens (host) and the vectors derived from them; fills `e`; throws if a row would pass llm_max_seq
+  void ext_upload(hipStream_t s, const int32_t* pos0, const int32_t* lens, int B, int n, PrefillExt& e);
+  // the verification pass of generate(): rows k[b] of the staged draft behind slen[b]; leaves the accept step's outputs in
+  // drf_host_ (after ev_tok_[0]) and the decode-step state for whatever follows
+  void draft_verify(hipStream_t s, int B, const std::vector<int>& slen, const std::vector<std::vector<int64_t>>& d,
+                    const std::vector<int>& k);
   // blocks [blk0, blk1) of the encoder; blk0 == 0 also runs the patch embedding, blk1 < 0 (= to the end) the neck
   void sam_encoder(hipStream_t s, const float* images, int B, float* out, int blk0 = 0, int blk1 = -1);
   void mask_decoder(hipStream_t s, const float* image_emb, const float* pred_emb, int n, float* masks4,
@@ -1393,10 +1427,12 @@ void Model<T, TS>::project_audio(hipStream_t s, const float* audio_emb, int n, f
 // LLaMA
 // ---------------------------------------------------------------------------------------------
 template <typename T, typename TS>
-void Model<T, TS>::llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev, bool keep_q) {
+void Model<T, TS>::llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev, bool keep_q, const PrefillExt* ext) {
   // l_x_ holds the spliced embeddings [B,Sp,H] (compact).  Fills the KV cache, hidden_all_[b, 0:Sp]
   // (post final norm) and next_dev_ (greedy token after each prompt).
+  // With ext the same rows run behind a cache: RoPE / append at pos0[b] + i, keys [0, pos0[b] + i], hidden_all_[b, pos0[b] + i].
   const anyref_config& c = cfg;
+  const int* pos0 = ext ? ext->pos0 : nullptr;
   const int H = c.llm_dim, F = c.llm_mlp, nh = c.llm_heads, hd = H / nh, S = c.llm_max_seq, R = B * Sp;
   const int nl = c.llm_layers;
   bool h_ready = false;  // l_h_ already holds in_norm(x) (fused into the previous layer's down_proj reduction)
@@ -1412,11 +1448,11 @@ void Model<T, TS>::llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev
       a.A = l_h_; a.lda = H; a.W = L.qkv.w; a.ldw = L.qkv.stride(); a.M = R; a.N = 3 * H; a.K = H;
       a.slabs_out = qkv_slabs_; a.slabs = 2;
       launch_gemm<T>(a, s);
-      launch_rope_cache_slabs<Q>(qkv_slabs_, qkv_slabs_ + (size_t)R * 3 * H, B, Sp, nh, hd, nullptr, lens_dev, rope_tab_, l_q_,
+      launch_rope_cache_slabs<Q>(qkv_slabs_, qkv_slabs_ + (size_t)R * 3 * H, B, Sp, nh, hd, pos0, lens_dev, rope_tab_, l_q_,
                                  kc, vc, S, qkeep, s);
     } else {
       gemm(s, l_h_, H, L.qkv, l_qkv_, 3 * H, R, ACT_NONE, QF32);
-      launch_rope_cache<Q>(l_qkv_, B, Sp, nh, hd, nullptr, lens_dev, rope_tab_, l_q_, kc, vc, S, qkeep, s);
+      launch_rope_cache<Q>(l_qkv_, B, Sp, nh, hd, pos0, lens_dev, rope_tab_, l_q_, kc, vc, S, qkeep, s);
     }
     AttnArgs a;
     a.Q = l_q_; a.K = kc; a.V = vc; a.O = l_att_;
@@ -1426,6 +1462,9 @@ void Model<T, TS>::llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev
     a.B = B; a.H = nh; a.Sq = Sp; a.Sk = Sp; a.hd = hd;
     a.scale = 1.f / sqrtf((float)hd);
     a.causal = 1; a.kv_len = lens_dev; a.q_len = lens_dev;
+    if (ext) {
+      a.q_pos0 = pos0; a.kv_len = ext->kv_len; a.Sk = ext->Sk;
+    }
     a.o_split = OSPT; a.sp16 = SPT;
     launch_attention<Q>(a, s);
     if (!gemm(s, l_att_, H, L.o, l_x_, H, R, ACT_NONE, true, l_x_, H, nullptr, &L.post_norm, l_h_))
@@ -1433,6 +1472,10 @@ void Model<T, TS>::llm_prefill(hipStream_t s, int B, int Sp, const int* lens_dev
     gemm(s, l_h_, H, L.gu, l_act_, F, R, ACT_NONE, false, nullptr, 0, nullptr, nullptr, nullptr, true);  // silu(g) * u
     h_ready = gemm(s, l_act_, F, L.down, l_x_, H, R, ACT_NONE, true, l_x_, H, nullptr,
                    i + 1 < nl ? &llm_layers_[i + 1].in_norm : nullptr, l_h_);
+  }
+  if (ext) {  // only the valid rows, each to its own position
+    norm(s, l_x_, H, llm_norm_, hidden_all_, H, R, H, c.llm_rms_eps, true, true, ext->hid_rows);
+    return;
   }
   for (int b = 0; b < B; ++b)
     norm(s, l_x_ + (size_t)b * Sp * H, H, llm_norm_, hidden_all_ + (size_t)b * S * H, H, Sp, H, c.llm_rms_eps, true,
@@ -1531,6 +1574,109 @@ void Model<T, TS>::llm_forward(hipStream_t s, const float* embeds, const int32_t
       launch_attn_row_mean<Q>(q_last_ + ((size_t)b * S + attn_q[b]) * H, 0, hd, kc + (size_t)b * S * H, 0, H, hd,
                               kvlen_dev_ + b, 1, nh, hd, 1.f / sqrtf((float)hd), attn_row + (size_t)b * Sn, Sn, s);
   }
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::ensure_ext() {
+  if (ext_idx_) return;
+  const size_t n = (size_t)3 * cfg.max_batch + (size_t)cfg.max_batch * cfg.llm_max_seq;
+  HIP_TRY(hipHostMalloc((void**)&ext_stage_, sizeof(int) * n));
+  HIP_TRY(hipEventCreateWithFlags(&ext_ev_, hipEventDisableTiming));
+  ext_idx_ = talloc<int>(n);
+}
+template <typename T, typename TS>
+void Model<T, TS>::ensure_draft() {
+  if (drf_ids_) return;
+  const size_t MB = cfg.max_batch, K = kDraftCap;
+  HIP_TRY(hipHostMalloc((void**)&drf_host_, sizeof(int64_t) * MB * (2 * K + 2)));
+  drf_p_ = talloc<int64_t>(MB * K);
+  drf_tok_ = talloc<int64_t>(MB * (K + 1));
+  drf_acc_ = talloc<int>(MB);
+  drf_logits_ = talloc<float>(MB * K * (size_t)cfg.llm_vocab);
+  drf_ids_ = talloc<int64_t>(MB * K);
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::ext_upload(hipStream_t s, const int32_t* pos0, const int32_t* lens, int B, int n, PrefillExt& e) {
+  const int S = cfg.llm_max_seq, MB = cfg.max_batch;
+  if (!pos0 || !lens) throw std::runtime_error("llm_extend: pos0 / lens are NULL");
+  if (B < 1 || B > MB || n < 1 || n > S) throw std::runtime_error("llm_extend: batch / rows exceed the model's limits");
+  int Sk = 1;
+  for (int b = 0; b < B; ++b) {
+    if (pos0[b] < 0 || lens[b] < 0 || lens[b] > n) throw std::runtime_error("llm_extend: bad pos0 / lens");
+    if (pos0[b] + lens[b] > S) throw std::runtime_error("llm_extend: pos0 + lens exceeds llm_max_seq");
+    Sk = std::max(Sk, pos0[b] + lens[b]);
+  }
+  ensure_ext();
+  if (ext_busy_) HIP_TRY(hipEventSynchronize(ext_ev_));  // the previous pass's copy still reads the pinned region
+  ext_busy_ = false;
+  int* st = ext_stage_;
+  for (int b = 0; b < B; ++b) {
+    st[b] = pos0[b];
+    st[MB + b] = lens[b];
+    st[2 * MB + b] = pos0[b] + lens[b];
+    for (int i = 0; i < n; ++i) st[3 * MB + b * n + i] = i < lens[b] ? b * S + pos0[b] + i : -1;
+  }
+  HIP_TRY(hipMemcpyAsync(ext_idx_, st, sizeof(int) * ((size_t)3 * MB + (size_t)B * n), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(ext_ev_, s));
+  ext_busy_ = true;
+  e.pos0 = ext_idx_;
+  e.lens = ext_idx_ + MB;
+  e.kv_len = ext_idx_ + 2 * MB;
+  e.hid_rows = ext_idx_ + 3 * MB;
+  e.Sk = Sk;
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::llm_extend(hipStream_t s, const float* embeds, const int32_t* pos0, const int32_t* lens, int B, int n,
+                              float* hidden, float* logits) {
+  HIP_TRY(hipSetDevice(device_));
+  if (!finalized_) throw std::runtime_error("llm_extend before finalize");
+  const anyref_config& c = cfg;
+  const int H = c.llm_dim, S = c.llm_max_seq;
+  PrefillExt e;
+  ext_upload(s, pos0, lens, B, n, e);
+  HIP_TRY(hipMemcpyAsync(l_x_, embeds, (size_t)B * n * H * 4, hipMemcpyDeviceToDevice, s));
+  llm_prefill(s, B, n, e.lens, false, &e);
+  for (int b = 0; b < B; ++b) {
+    if (lens[b] == 0) continue;
+    const float* rows = hidden_all_ + ((size_t)b * S + pos0[b]) * H;
+    HIP_TRY(hipMemcpyAsync(hidden + (size_t)b * n * H, rows, (size_t)lens[b] * H * 4, hipMemcpyDeviceToDevice, s));
+    if (logits) launch_convert<T>(rows, H, l_h_ + (size_t)b * n * apad<T>(H), apad<T>(H), lens[b], H, s);
+  }
+  if (logits) gemm(s, l_h_, H, lm_head_, logits, c.llm_vocab, B * n, ACT_NONE, true);
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::draft_verify(hipStream_t s, int B, const std::vector<int>& slen, const std::vector<std::vector<int64_t>>& d,
+                                const std::vector<int>& k) {
+  const anyref_config& c = cfg;
+  const int H = c.llm_dim, S = c.llm_max_seq, V = c.llm_vocab;
+  int n = 0;
+  for (int b = 0; b < B; ++b) n = std::max(n, k[b]);
+  if (n < 1 || n > kDraftCap) throw std::runtime_error("internal: draft rows outside [1, 64]");
+  ensure_draft();
+  // (the host waited for the previous pass's results before it returned: the pinned id region is free)
+  int64_t* ids_h = drf_host_;
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < n; ++i) ids_h[(size_t)b * n + i] = i < k[b] ? d[b][i] : 0;
+  PrefillExt e;
+  ext_upload(s, slen.data(), k.data(), B, n, e);
+  HIP_TRY(hipMemcpyAsync(drf_ids_, ids_h, (size_t)B * n * 8, hipMemcpyHostToDevice, s));
+  launch_embed_rows(drf_ids_, B * n, emb_table_, kEmbDtype, H, l_x_, s);
+  llm_prefill(s, B, n, e.lens, false, &e);
+  for (int b = 0; b < B; ++b)
+    if (k[b] > 0)
+      launch_convert<T>(hidden_all_ + ((size_t)b * S + slen[b]) * H, H, l_h_ + (size_t)b * n * apad<T>(H), apad<T>(H), k[b], H, s);
+  gemm(s, l_h_, H, lm_head_, drf_logits_, V, B * n, ACT_NONE, true);
+  launch_draft_accept(drf_logits_, B, n, V, V, drf_p_, drf_ids_, e.lens, next_dev_, pos_dev_, drf_tok_, drf_acc_, emb_table_,
+                      kEmbDtype, H, S, d_x_, rowmap_dev_, kvlen_dev_, s);
+  int64_t* tok_h = drf_host_ + (size_t)c.max_batch * kDraftCap;
+  int* acc_h = reinterpret_cast<int*>(tok_h + (size_t)c.max_batch * (kDraftCap + 1));
+  HIP_TRY(hipMemcpyAsync(tok_h, drf_tok_, (size_t)B * (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(acc_h, drf_acc_, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipEventRecord(ev_tok_[0], s));
+  HIP_TRY(hipEventSynchronize(ev_tok_[0]));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1989,11 +2135,18 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
                         int n_extra, const int32_t* resized_hw, const int32_t* orig_hw, int max_new_tokens,
                         int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
                         int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) {
+  // the one-shot draft (anyref_set_draft) is taken here: whatever happens below, nothing stays armed
+  std::vector<std::vector<int64_t>> draft;
+  draft.swap(draft_ids_);
   HIP_TRY(hipSetDevice(device_));
   const anyref_config& c = cfg;
+  stat_offered_.assign(B > 0 ? B : 0, 0);
+  stat_accepted_.assign(B > 0 ? B : 0, 0);
+  stat_steps_ = stat_passes_ = 0;
   if (!finalized_) throw std::runtime_error("generate before finalize");
   if (B <= 0 || B > c.max_batch) throw std::runtime_error("batch exceeds max_batch");
   if (max_new_tokens < 1) throw std::runtime_error("max_new_tokens must be >= 1");
+  if (!draft.empty() && (int)draft.size() != B) throw std::runtime_error("the pending draft was set for another batch size");
   const int H = c.llm_dim, S = c.llm_max_seq, n_img = clip_n_;
   const bool keep_q = c.rephrase_weight > 0.f;
 
@@ -2096,12 +2249,81 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
     if (!sam_enq_done_) return true;
     return corun_tail-- > 0;
   };
-  for (int step = 0; step < max_new_tokens; ++step) {
+  // ---- draft-verified decode (anyref_set_draft) ----
+  // The draft of every row is cut to what may be fed (cut_draft in anyref_amd/draft.py states the same rules); with nothing
+  // left the plain loop below runs, launch for launch as without a draft.
+  std::vector<int> dk(B, 0);
+  bool drafted = false;
+  if (!draft.empty() && !keep_q) {  // rephrasing reads the attention of the whole answer: the draft is ignored (offered = 0)
+    for (int b = 0; b < B; ++b) {
+      int k = 0;
+      while (k < (int)draft[b].size() && draft[b][k] >= 0 && draft[b][k] < c.llm_vocab) ++k;
+      k = std::min(k, std::min(max_new_tokens - 1, (int)kDraftCap));
+      // B > 1: a row that gets ahead keeps stepping while slower rows finish, and must stay inside the cache
+      if (B > 1) k = std::min(k, S - slen[b] - max_new_tokens);
+      dk[b] = std::max(k, 0);
+      drafted = drafted || dk[b] > 0;
+    }
+  }
+  if (drafted) {
+    // rows end one by one here: at their EOS or with max_new_tokens tokens
+    auto push = [&](int b, int64_t t, hipEvent_t ready) {
+      if (fin[b]) return;
+      const int g = (int)gen[b].size();  // token g was predicted by hidden row slen + g - 1, final once `ready` has passed
+      gen[b].push_back(t);
+      if (eos_token_id >= 0 && t == eos_token_id) fin[b] = 1;
+      if (g + 1 >= max_new_tokens) fin[b] = 1;
+      if (early && !early_stop_ && t >= c.seg_lo && t <= c.seg_hi)
+        early_seg(ready, slen[0] + g - 1, resized_hw, orig_hw, out_masks, out_masks_cap, out_low);
+    };
+    // the first token decides whether a row's draft is worth a pass at all
+    int64_t* t0 = next_host_;
+    HIP_TRY(hipMemcpyAsync(t0, next_dev_, B * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(ev_tok_[0], s));
+    HIP_TRY(hipEventSynchronize(ev_tok_[0]));
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+      if (dk[b] > 0 && t0[b] != draft[b][0]) dk[b] = 0;  // what is left of a draft after a mismatch is dropped
+      any = any || dk[b] > 0;
+    }
+    if (any) {
+      int n = 0;
+      for (int b = 0; b < B; ++b) n = std::max(n, dk[b]);
+      draft_verify(s, B, slen, draft, dk);  // waits for the accept step's results
+      stat_passes_ = 1;
+      const int64_t* tok_h = drf_host_ + (size_t)c.max_batch * kDraftCap;
+      const int* acc_h = reinterpret_cast<const int*>(tok_h + (size_t)c.max_batch * (kDraftCap + 1));
+      for (int b = 0; b < B; ++b) {
+        stat_offered_[b] = dk[b];
+        stat_accepted_[b] = acc_h[b];
+        for (int j = 0; j <= acc_h[b]; ++j) push(b, tok_h[(size_t)b * (n + 1) + j], ev_tok_[0]);
+      }
+    } else {
+      for (int b = 0; b < B; ++b) push(b, t0[b], ev_tok_[0]);
+    }
+    // the rest one token at a time; rows differ in how many tokens they hold, so the stop test is per row (the host sees
+    // every token before it queues the next step, as the plain loop does with an EOS id)
+    for (int it = 0;; ++it) {
+      bool all = true;
+      for (int b = 0; b < B; ++b) all = all && fin[b];
+      if (all) break;
+      decode_step_graph(s, B, keep_q, corun_step());
+      ++stat_steps_;
+      if (fed) sam_feed(sam_next_blk_ + per_step, true);
+      int64_t* tok = next_host_ + (size_t)(it & 1) * c.max_batch;
+      HIP_TRY(hipMemcpyAsync(tok, next_dev_, B * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipEventRecord(ev_tok_[it & 1], s));
+      HIP_TRY(hipEventSynchronize(ev_tok_[it & 1]));
+      for (int b = 0; b < B; ++b) push(b, tok[b], ev_tok_[it & 1]);
+    }
+  }
+  for (int step = 0; !drafted && step < max_new_tokens; ++step) {
     int64_t* tok = next_host_ + (size_t)(step & 1) * c.max_batch;
     const bool last = step == max_new_tokens - 1;
     HIP_TRY(hipMemcpyAsync(tok, next_dev_, B * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(ev_tok_[step & 1], s));
     if (ahead && !last) {
+      ++stat_steps_;
       decode_step_graph(s, B, keep_q, corun_step());
       if (fed) sam_feed(sam_next_blk_ + per_step, true);  // the encoder's share of this step (host is idle until the token)
     }
@@ -2119,6 +2341,7 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
     }
     if (all || last) break;
     if (!ahead) {
+      ++stat_steps_;
       decode_step_graph(s, B, keep_q, corun_step());
       if (fed) sam_feed(sam_next_blk_ + per_step, true);
     }
@@ -2158,6 +2381,7 @@ void Model<T, TS>::forward_teacher(hipStream_t s, const float* clip_images, cons
                                const int32_t* rephrase_start, const int32_t* resized_hw, const int32_t* orig_hw,
                                int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
                                float* out_low, float* out_hidden, float* out_logits) {
+  draft_ids_.clear();  // a draft is a hint for generate: a teacher-forced call in between drops it
   HIP_TRY(hipSetDevice(device_));
   const anyref_config& c = cfg;
   if (!finalized_) throw std::runtime_error("forward before finalize");

@@ -1130,6 +1130,58 @@ void launch_argmax_next(const float* x, int M, int N, int ldx, int64_t* out, int
   hipLaunchKernelGGL(argmax_kernel, dim3(M), dim3(1024), 0, s, x, N, ldx, out, pos, nx);
 }
 
+// Accept step of a draft-verified greedy decode.  Row b of the verification pass fed the draft d[0 .. k_b) at
+// positions pos[b] ..; p[i] is the argmax of its logits row i (argmax_kernel above, one workgroup per row).  With g[0] = next[b]
+// (the token prefill chose) and g[j + 1] = p[j], the accepted count m is the number of leading j < k_b with g[j] == d[j]:
+// g[0 .. m] are then exactly the tokens the one-token loop would have produced.  One workgroup per sequence: thread 0 walks
+// the (<= kDraftAcceptMaxK) pairs staged in LDS and leaves the state launch_argmax_next leaves -- next = g[m], pos += m,
+// row_map, kvlen -- then every thread copies the embedding row of g[m].  Plain vector stores only.
+constexpr int kDraftAcceptMaxK = 256;
+__global__ __launch_bounds__(256) void draft_accept_kernel(const int64_t* __restrict__ p, const int64_t* __restrict__ draft,
+                                                           const int* __restrict__ dlen, int k, int64_t* __restrict__ next,
+                                                           int* __restrict__ pos, int64_t* __restrict__ tokens,
+                                                           int* __restrict__ accepted, ArgmaxNext nx) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  __shared__ int64_t sp[kDraftAcceptMaxK], sd[kDraftAcceptMaxK];
+  __shared__ int64_t s_id;
+  int kb = dlen[b];
+  kb = kb < 0 ? 0 : (kb > k ? k : kb);
+  if (tid < kb) {
+    sp[tid] = p[(int64_t)b * k + tid];
+    sd[tid] = draft[(int64_t)b * k + tid];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int64_t* tb = tokens + (int64_t)b * (k + 1);
+    int64_t g = next[b];
+    int m = 0;
+    tb[0] = g;
+    while (m < kb && g == sd[m]) {
+      g = sp[m];
+      tb[++m] = g;
+    }
+    accepted[b] = m;
+    next[b] = g;
+    const int ps = pos[b] + m;
+    pos[b] = ps;
+    nx.row_map[b] = b * nx.maxS + ps;
+    nx.kvlen[b] = ps + 1;
+    s_id = g;
+  }
+  __syncthreads();
+  table_row_to_f32(nx.table, nx.dtype, s_id, nx.D, nx.x + (int64_t)b * nx.D, tid, 256);
+}
+void launch_draft_accept(const float* logits, int B, int k, int N, int ldx, int64_t* p, const int64_t* draft, const int* dlen,
+                         int64_t* next, int* pos, int64_t* tokens, int* accepted, const void* table, int dtype, int D, int maxS,
+                         float* x_next, int* row_map, int* kvlen, hipStream_t s) {
+  if (B <= 0) return;
+  if (k < 1 || k > kDraftAcceptMaxK) throw std::runtime_error("draft_accept: 1 <= k <= 256");
+  launch_argmax(logits, B * k, N, ldx, p, s);
+  ArgmaxNext nx;
+  nx.table = table; nx.dtype = dtype; nx.D = D; nx.maxS = maxS; nx.x = x_next; nx.row_map = row_map; nx.kvlen = kvlen;
+  hipLaunchKernelGGL(draft_accept_kernel, dim3(B), dim3(256), 0, s, p, draft, dlen, k, next, pos, tokens, accepted, nx);
+}
+
 // ---------------------------------------------------------------------------------------------
 // mask-decoder upscaler tails
 // ---------------------------------------------------------------------------------------------

@@ -328,6 +328,18 @@ int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_
   });
 }
 
+int anyref_op_draft_accept(void* stream, const float* logits, int B, int k, int N, int ldx, int64_t* p, const int64_t* draft,
+                           const int32_t* draft_lens, int64_t* next, int32_t* pos, int64_t* tokens, int32_t* accepted,
+                           const void* table, int dtype, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen) {
+  OP_GUARD({
+    if (dtype < 0 || dtype > 2) throw std::runtime_error("op_draft_accept: table dtype 0 / 1 / 2");
+    if (!logits || !p || !draft || !draft_lens || !next || !pos || !tokens || !accepted || !table || !x_next || !row_map || !kvlen)
+      throw std::runtime_error("op_draft_accept: null argument");
+    launch_draft_accept(logits, B, k, N, ldx, p, draft, draft_lens, next, pos, tokens, accepted, table, dtype, D, maxS, x_next,
+                        row_map, kvlen, (hipStream_t)stream);
+  });
+}
+
 int anyref_op_norm(int t, void* stream, const float* x, const float* gain, const float* bias, float* y, int M,
                    int D, float eps, int rms) {
   OP_GUARD({

@@ -68,7 +68,7 @@ def _c_config(cfg: AnyRefConfig, mode: int, max_batch: int, max_seg: int) -> _li
 _NEEDS_HANDLE = frozenset({
     "generate", "model_forward_new", "forward", "__call__", "encode_images", "sam_encode", "mask_decode", "llm_forward",
     "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
-    "stamps_enable", "stamps_read", "set_side_share"})
+    "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats"})
 
 
 class AnyRefForCausalLM:
@@ -108,6 +108,8 @@ class AnyRefForCausalLM:
         # The reference's success path itself returns 2 values (anyref.py:822), which is what eval_refer_inv.py:135 and
         # eval_coco20i.py:142 unpack: set `model.success_arity = 2` for those scripts.
         self.success_arity = 3
+        self._draft_policy: Optional[str] = None     # set_draft_policy
+        self._last_answers: Optional[List[List[int]]] = None
         # `from_pretrained` flow: weights are gathered on the host first (base checkpoint, CLIP tower, SAM file,
         # token-row resize, LoRA merge all happen BEFORE `.cuda()` in the callers) and go to HBM in one build
         self._host_sd: Optional[Dict[str, torch.Tensor]] = {} if defer else None
@@ -364,6 +366,40 @@ class AnyRefForCausalLM:
         """Workgroup cap of the SAM encoder's GEMM / attention launches while it co-runs with the decode loop (0: none),
         and the number of decode steps its blocks are spread over (0: keep)."""
         self._check(self.lib.anyref_set_side_share(self.h, int(wgs), int(steps)), "set_side_share")
+
+    # ---- draft-verified greedy decode (anyref_set_draft) ----------------------------------------
+    def set_draft_policy(self, policy: Optional[str]):
+        """`"last"`: a `generate` call without `draft_ids` proposes, per row index, the tokens that row generated in the
+        previous call with the same batch size -- the eval loops, whose answers are one of a few fixed templates, then have
+        the answer checked in one pass over the weights instead of one per token.  `None` (default): no draft unless the
+        caller passes one.  A draft never changes what is generated."""
+        if policy not in (None, "last"):
+            raise ValueError('draft policy is "last" or None')
+        self._draft_policy = policy
+        self._last_answers = None
+
+    def set_draft(self, drafts):
+        """One-shot proposal for the next `generate` (cleared by the next generate / forward whether used or not):
+        a list of B token lists (empty / None: no draft for that row), or None to cancel."""
+        if drafts is None:
+            self._check(self.lib.anyref_set_draft(self.h, None, None, 0, 0), "set_draft")
+            return
+        rows = [[] if d is None else [int(v) for v in d] for d in drafts]
+        B, K = len(rows), max(1, max(len(r) for r in rows))
+        ids = torch.zeros(B, K, dtype=torch.long)
+        for b, r in enumerate(rows):
+            ids[b, : len(r)] = torch.tensor(r, dtype=torch.long)
+        lens = torch.tensor([len(r) for r in rows], dtype=torch.int32)
+        self._check(self.lib.anyref_set_draft(self.h, _ptr(ids), _ptr(lens), B, K), "set_draft")
+
+    def draft_stats(self, B: int):
+        """Of the last `generate`: dict(draft_offered i32 [B], draft_accepted i32 [B], decode_steps, verify_passes)."""
+        off = torch.zeros(B, dtype=torch.int32)
+        acc = torch.zeros(B, dtype=torch.int32)
+        steps, passes = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.anyref_draft_stats(self.h, _ptr(off), _ptr(acc), B, C.byref(steps), C.byref(passes)),
+                    "draft_stats")
+        return dict(draft_offered=off, draft_accepted=acc, decode_steps=int(steps.value), verify_passes=int(passes.value))
 
     # ---- per-kernel timing for bench.py ------------------------------------------------------
     def profile_enable(self, on: bool, only_tag: Optional[str] = None, sample_every: int = 1):
@@ -622,6 +658,21 @@ class AnyRefForCausalLM:
                                                 aq, _ptr(ar)), "llm_forward")
         return dict(hidden=hidden, logits=logits, attn_row=ar)
 
+    def llm_extend(self, embeds: torch.Tensor, pos0: Sequence[int], lens: Optional[Sequence[int]] = None,
+                   want_logits: bool = False):
+        """`anyref_llm_extend`: n new rows per sequence behind the KV cache the previous `llm_forward` / `llm_extend` left,
+        row i of sequence b at position pos0[b] + i.  -> dict(hidden [B,n,H], logits [B,n,vocab] | None); hidden rows at and
+        past lens[b] are NaN (never written), logits rows there are undefined."""
+        x = embeds.to(self.device, torch.float32).contiguous()
+        B, n, H = x.shape
+        p0 = (C.c_int32 * B)(*[int(v) for v in pos0])
+        ln = (C.c_int32 * B)(*([n] * B if lens is None else [int(v) for v in lens]))
+        hidden = torch.full((B, n, H), float("nan"), device=self.device, dtype=torch.float32)
+        logits = torch.empty(B, n, self.cfg.llm.vocab, device=self.device, dtype=torch.float32) if want_logits else None
+        self._check(self.lib.anyref_llm_extend(self.h, self._stream(), _ptr(x), p0, ln, B, n, _ptr(hidden), _ptr(logits)),
+                    "llm_extend")
+        return dict(hidden=hidden, logits=logits)
+
     def seg_tail(self, sam_images, ids, ids_lens, ref_pos, hidden, attn_mean, sam_resized_sizes, height, width,
                  teacher: bool = False):
         """The glue alone (anyref.py:718-822 / :273-282,:356-430) on caller-provided LLM outputs:
@@ -654,12 +705,23 @@ class AnyRefForCausalLM:
     @torch.no_grad()
     def generate(self, clip_images, input_ids, sam_images, sam_resized_sizes, height, width, audios=None,
                  ref_images=None, output_hidden_states=True, return_dict_in_generate=True, max_new_tokens=128,
-                 attention_masks=None, _return_extras: bool = False):
-        """`AnyRefForCausalLM.generate` (model/anyref.py:647-822)."""
+                 attention_masks=None, _return_extras: bool = False, draft_ids=None):
+        """`AnyRefForCausalLM.generate` (model/anyref.py:647-822).
+
+        `draft_ids` (trailing keyword, not in the reference): a proposed answer per row -- the generated tokens from the
+        first one on -- as a list of B 1-D tensors / lists (None entries allowed) or a [B, K] tensor whose rows end at the
+        first negative id.  The backend checks it in one pass over the weights and falls back to the one-token loop where it
+        stops matching; the output is the same greedy decode either way (`set_draft_policy`)."""
         ids, lens = self._rows(input_ids, attention_masks)
         B, Lmax = ids.shape
         if B > self.max_batch:
             raise ValueError(f"batch {B} > max_batch {self.max_batch} the handle was created for")
+        drafts = None
+        if draft_ids is not None:
+            from .draft import normalize_drafts
+            drafts = normalize_drafts(draft_ids, B)
+        elif self._draft_policy == "last" and self._last_answers is not None and len(self._last_answers) == B:
+            drafts = self._last_answers
         clip = clip_images.to(self.device, torch.float32).contiguous()
         sam = sam_images.to(self.device, torch.float32).contiguous()
         extra, slots, n_extra = self._extra_overlapped(ids, lens, audios, self._ref_features(ref_images, B))
@@ -681,10 +743,14 @@ class AnyRefForCausalLM:
             if _return_extras != "low":
                 hid = torch.empty(B, self.cfg.llm.max_seq, self.cfg.llm.dim, device=self.device, dtype=torch.float32)
         eos = self.config.eos_token_id if self.config.eos_token_id is not None else -1
+        if drafts is not None and any(drafts):
+            self.set_draft(drafts)
         self._check(self.lib.anyref_generate(
             self.h, self._stream(), _ptr(clip), _ptr(sam), _ptr(ids), _ptr(lens), B, Lmax, _ptr(extra),
             _ptr(slots), n_extra, _ptr(rs), _ptr(os_), int(max_new_tokens), int(eos), _ptr(out_ids), _ptr(out_lens),
             _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)), "generate")
+        if self._draft_policy == "last":
+            self._last_answers = [out_ids[b, int(lens[b]): int(out_lens[b])].tolist() for b in range(B)]
         # HF pads finished rows with pad_token_id
         full = torch.full((B, int(out_lens.max())), int(self.config.pad_token_id or 0), dtype=torch.long)
         for b in range(B):
@@ -709,7 +775,7 @@ class AnyRefForCausalLM:
         if self.success_arity == 2 and res[1] is not None and not (self.cfg.rephrase_weight > 0 and total < B):
             res = res[:2]                                 # the reference's own success path (anyref.py:822): any [SEG], no `no_mask`
         if _return_extras:
-            return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid)
+            return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **self.draft_stats(B))
         return res
 
     def forward(self, **kwargs):

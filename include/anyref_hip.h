@@ -186,6 +186,13 @@ int anyref_mask_decode(anyref_handle* h, void* stream, const float* image_emb, c
  * query `attn_q[b]` (i32[B] host) over all keys (anyref.py:748-749). */
 int anyref_llm_forward(anyref_handle* h, void* stream, const float* embeds, const int32_t* lens, int B,
                        int S, float* hidden, float* logits, const int32_t* attn_q, float* attn_row);
+/* n new rows per sequence behind the KV cache left by the previous anyref_llm_forward / anyref_llm_extend on
+ * this handle.  embeds f32 [B,n,dim] dev; pos0, lens i32 [B] host (rows already cached; valid rows <= n);
+ * hidden f32 [B,n,dim] dev (post final norm; rows >= lens[b] are left as they were); logits f32 [B,n,vocab] dev or NULL
+ * (rows >= lens[b] undefined).  Error if pos0[b] + lens[b] > llm_max_seq.  The pass is the prefill code path at a position
+ * offset: RoPE / cache append at pos0[b] + i, causal attention over keys [0, pos0[b] + i]. */
+int anyref_llm_extend(anyref_handle* h, void* stream, const float* embeds, const int32_t* pos0,
+                      const int32_t* lens, int B, int n, float* hidden, float* logits);
 
 /* ImageBindModel.get_audio_feature, second return value (model/ImageBind/models/imagebind_model.py:477-511; call
  * sites anyref.py:313-315, :670-672), for handles created with aud_blocks > 0 and given the
@@ -242,6 +249,26 @@ int anyref_set_early_tail(anyref_handle* h, int on);
  * place the rows are read -- so the trunk runs beside the CLIP tower instead of in front of the call.  One-shot: cleared
  * by the call that consumes it; NULL cancels.  The event must stay alive until that call has been queued. */
 int anyref_set_extra_event(anyref_handle* h, void* event);
+
+/* Draft-verified greedy decode.  The answers of this model are nearly constant, so a caller can propose
+ * the expected continuation and have all of it checked in ONE multi-row pass over the weights instead of one pass per token.
+ * Proposed continuation for the NEXT anyref_generate on this handle: draft_ids i64 [B,Kmax] host, draft_lens i32 [B]
+ * (0 = no draft for that row).  Copied.  One-shot: cleared at the entry of the next anyref_generate /
+ * anyref_forward_teacher whether it is used or not, and on error.  NULL cancels.  A draft never changes what is
+ * generated, only how many passes it takes.
+ * After prefill has chosen the first token t0, row b's draft d is cut at the first id outside [0, vocab), to
+ * max_new_tokens - 1, to 64 and, for B > 1, to llm_max_seq - slen[b] - max_new_tokens (slen = spliced prompt length: a row
+ * that gets ahead keeps stepping while slower rows finish and must stay inside the cache); a row whose t0 != d[0] offers
+ * nothing.  If any row offers k_b >= 1 tokens, one pass runs d[0 .. k_b) at positions slen[b] .. (anyref_llm_extend's path),
+ * lm_head on those rows and the accept step (anyref_op_draft_accept): with g[0] = t0, g[j + 1] = argmax(logits[j]), the
+ * accepted count m_b is the number of leading j < k_b with g[j] == d[j], and g[0 .. m_b] are appended to the row (EOS and
+ * max_new_tokens applied per row).  The one-token loop then continues, graph replay included, until every row has ended.
+ * At most one verification pass per call.  With rephrase_weight > 0 the draft is ignored (offered = 0). */
+int anyref_set_draft(anyref_handle* h, const int64_t* draft_ids, const int32_t* draft_lens, int B, int Kmax);
+/* After anyref_generate: per row, the draft tokens fed to the verification pass and how many were accepted;
+ * decode steps launched by the call; verification passes (0 or 1).  Any pointer may be NULL. */
+int anyref_draft_stats(anyref_handle* h, int32_t* offered, int32_t* accepted, int B, int32_t* decode_steps,
+                       int32_t* verify_passes);
 
 /* hipGraph replay of the greedy decode step (default 1): one step is ~170 launches with fixed
  * arguments (position / next token live on the device), captured once per batch size.  0 launches

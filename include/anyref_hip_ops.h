@@ -50,6 +50,15 @@ int anyref_op_rope_cache(int t, void* stream, const void* qkv, const float* slab
  * b * maxS + pos[b], kvlen[b] = pos[b] + 1 (pos required) */
 int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_t* out, int32_t* pos, const void* table,
                      int is_bf16, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen);
+/* accept step of the draft-verified greedy decode (anyref_set_draft): logits f32 [B * k, N] (row stride ldx) of a verification
+ * pass that fed draft i64 [B, k] (draft_lens[b] <= k valid ids per row, 0 = none) behind next[b], the token already chosen.
+ * p i64 [B * k] receives the row argmaxes (first index on ties).  Per row, with g[0] = next[b], g[j + 1] = p[j]: accepted[b] = m =
+ * number of leading j < draft_lens[b] with g[j] == draft[b, j]; tokens i64 [B, k + 1] receives g[0 .. m]; and, as
+ * anyref_op_argmax leaves them: next[b] = g[m], pos[b] += m, x_next f32 [B, D] = table[g[m]] (dtype 0 = f32, 1 = bf16, 2 = f16),
+ * row_map[b] = b * maxS + pos[b], kvlen[b] = pos[b] + 1.  1 <= k <= 256. */
+int anyref_op_draft_accept(void* stream, const float* logits, int B, int k, int N, int ldx, int64_t* p, const int64_t* draft,
+                           const int32_t* draft_lens, int64_t* next, int32_t* pos, int64_t* tokens, int32_t* accepted,
+                           const void* table, int dtype, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen);
 /* LayerNorm (rms=0) / RMSNorm (rms=1); x f32, y f32 */
 int anyref_op_norm(int t, void* stream, const float* x, const float* gain, const float* bias, float* y, int M,
                    int D, float eps, int rms);
