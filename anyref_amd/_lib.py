@@ -95,6 +95,9 @@ SYMBOLS = {
     "anyref_llm_extend": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "anyref_set_draft": (_I, [_P, _P, _P, _I, _I]),
     "anyref_draft_stats": (_I, [_P, _P, _P, _I, _P, _P]),
+    "anyref_session_open": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
+    "anyref_session_generate": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
+    "anyref_session_close": (_I, [_P]),
     "anyref_project_audio": (_I, [_P, _P, _P, _I, _P]),
     "anyref_audio_encode": (_I, [_P, _P, _P, _I, _P]),
     "anyref_seg_tail": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _L, _P, _P]),
@@ -143,6 +146,7 @@ SYMBOLS = {
     "anyref_op_rope_cache": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "anyref_op_argmax": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_draft_accept": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "anyref_op_kv_broadcast": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),
     "anyref_op_norm": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _F, _I]),
     "anyref_op_attention": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _I, _I]),
     "anyref_op_attention_tab": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _I, _I]),

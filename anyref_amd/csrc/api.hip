@@ -66,7 +66,7 @@ int anyref_set_weight(anyref_handle* h, const char* name, const void* ptr, int i
   GUARD(h, h->m->set_weight(name, ptr, is_device, dtype, shape, ndim));
 }
 
-int anyref_finalize(anyref_handle* h) { GUARD(h, h->m->finalize()); }
+int anyref_finalize(anyref_handle* h) { GUARD(h, h->m->end_session("anyref_finalize"); h->m->finalize()); }
 
 int anyref_generate(anyref_handle* h, void* stream, const float* clip_images, const float* sam_images,
                     const int64_t* input_ids, const int32_t* lens, int B, int Lmax, const float* extra_embeds,
@@ -74,7 +74,7 @@ int anyref_generate(anyref_handle* h, void* stream, const float* clip_images, co
                     int max_new_tokens, int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg,
                     float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets, float* out_low,
                     float* out_hidden) {
-  GUARD(h, h->m->generate((hipStream_t)stream, clip_images, sam_images, input_ids, lens, B, Lmax, extra_embeds,
+  GUARD(h, h->m->end_session("anyref_generate"); h->m->generate((hipStream_t)stream, clip_images, sam_images, input_ids, lens, B, Lmax, extra_embeds,
                           extra_slots, n_extra, resized_hw, orig_hw, max_new_tokens, eos_token_id, out_ids,
                           out_lens, out_nseg, out_masks, out_masks_cap, mask_offsets, out_low, out_hidden));
 }
@@ -85,14 +85,14 @@ int anyref_forward_teacher(anyref_handle* h, void* stream, const float* clip_ima
                            const int32_t* rephrase_start, const int32_t* resized_hw, const int32_t* orig_hw,
                            int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
                            float* out_low, float* out_hidden, float* out_logits) {
-  GUARD(h, h->m->forward_teacher((hipStream_t)stream, clip_images, sam_images, input_ids, lens, B, Lmax,
+  GUARD(h, h->m->end_session("anyref_forward_teacher"); h->m->forward_teacher((hipStream_t)stream, clip_images, sam_images, input_ids, lens, B, Lmax,
                                  extra_embeds, extra_slots, n_extra, rephrase_start, resized_hw, orig_hw, out_nseg,
                                  out_masks, out_masks_cap, mask_offsets, out_low, out_hidden, out_logits));
 }
 
 int anyref_encode_images(anyref_handle* h, void* stream, const float* clip_images, int B, float* out,
                          float* clip_feat) {
-  GUARD(h, h->m->encode_images((hipStream_t)stream, clip_images, B, out, clip_feat));
+  GUARD(h, h->m->end_session("anyref_encode_images"); h->m->encode_images((hipStream_t)stream, clip_images, B, out, clip_feat));
 }
 
 int anyref_sam_encode(anyref_handle* h, void* stream, const float* sam_images, int B, float* out) {
@@ -107,13 +107,29 @@ int anyref_mask_decode(anyref_handle* h, void* stream, const float* image_emb, c
 
 int anyref_llm_forward(anyref_handle* h, void* stream, const float* embeds, const int32_t* lens, int B, int S,
                        float* hidden, float* logits, const int32_t* attn_q, float* attn_row) {
-  GUARD(h, h->m->llm_forward((hipStream_t)stream, embeds, lens, B, S, hidden, logits, attn_q, attn_row));
+  GUARD(h, h->m->end_session("anyref_llm_forward"); h->m->llm_forward((hipStream_t)stream, embeds, lens, B, S, hidden, logits, attn_q, attn_row));
 }
 
 int anyref_llm_extend(anyref_handle* h, void* stream, const float* embeds, const int32_t* pos0, const int32_t* lens, int B,
                       int n, float* hidden, float* logits) {
-  GUARD(h, h->m->llm_extend((hipStream_t)stream, embeds, pos0, lens, B, n, hidden, logits));
+  GUARD(h, h->m->end_session("anyref_llm_extend"); h->m->llm_extend((hipStream_t)stream, embeds, pos0, lens, B, n, hidden, logits));
 }
+
+int anyref_session_open(anyref_handle* h, void* stream, const float* clip_image, const float* sam_image,
+                        const int64_t* prefix_ids, int prefix_len, const int32_t* resized_hw, const int32_t* orig_hw) {
+  GUARD(h, h->m->session_open((hipStream_t)stream, clip_image, sam_image, prefix_ids, prefix_len, resized_hw, orig_hw));
+}
+
+int anyref_session_generate(anyref_handle* h, void* stream, const int64_t* suffix_ids, const int32_t* lens, int Q, int Lmax,
+                            const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
+                            int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
+                            int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) {
+  GUARD(h, h->m->session_generate((hipStream_t)stream, suffix_ids, lens, Q, Lmax, extra_embeds, extra_slots, n_extra,
+                                  max_new_tokens, eos_token_id, out_ids, out_lens, out_nseg, out_masks, out_masks_cap,
+                                  mask_offsets, out_low, out_hidden));
+}
+
+int anyref_session_close(anyref_handle* h) { GUARD(h, h->m->session_close()); }
 
 int anyref_set_draft(anyref_handle* h, const int64_t* draft_ids, const int32_t* draft_lens, int B, int Kmax) {
   GUARD(h, h->m->set_draft(draft_ids, draft_lens, B, Kmax));
@@ -136,7 +152,7 @@ int anyref_seg_tail(anyref_handle* h, void* stream, const float* sam_images, con
                     const int32_t* ids_lens, const int32_t* ref_pos, int B, int Lmax, int teacher, const float* hidden,
                     int hidden_rows, const float* attn_mean, const int32_t* resized_hw, const int32_t* orig_hw,
                     int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets, float* out_low) {
-  GUARD(h, h->m->seg_tail((hipStream_t)stream, sam_images, ids, ids_lens, ref_pos, B, Lmax, teacher, hidden,
+  GUARD(h, h->m->end_session("anyref_seg_tail"); h->m->seg_tail((hipStream_t)stream, sam_images, ids, ids_lens, ref_pos, B, Lmax, teacher, hidden,
                           hidden_rows, attn_mean, resized_hw, orig_hw, out_nseg, out_masks, out_masks_cap,
                           mask_offsets, out_low));
 }

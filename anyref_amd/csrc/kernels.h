@@ -396,6 +396,13 @@ void launch_rope_cache_f32(const float* qkv, int B, int H, int hd, const int* po
 void rope_table(int S, int hd, float theta, float* out);
 // token embedding rows for the decode step: x[b,:] = table[ids[b],:]
 void launch_embed_rows(const int64_t* ids, int B, const void* table, int dtype, int D, float* x, hipStream_t s);
+// Prefix broadcast of an image session: in every plane of a [planes][rows][maxS][row_bytes] buffer, bytes [0, P * row_bytes) of
+// row 0 are copied to rows [r0, r1).  base0 holds planes0 planes and base1 (may be null with planes1 = 0) planes1 more, both
+// plane_stride bytes apart -- the K and the V cache of every layer in one launch; the element type enters only through
+// row_bytes.  Each 16-byte piece is read once and stored r1 - r0 times (2-byte pieces when row_bytes is no multiple of 16).
+// P == 0 or r1 <= r0: nothing is launched.  Throws if P > maxS, r0 < 1 or r1 > rows.
+void launch_kv_broadcast(void* base0, int planes0, void* base1, int planes1, int64_t plane_stride, int rows, int maxS,
+                         int64_t row_bytes, int P, int r0, int r1, hipStream_t s);
 // row_map[b] = b*maxS + pos[b]; kvlen[b] = pos[b] + 1
 void launch_decode_index(const int* pos, int B, int maxS, int* row_map, int* kvlen, hipStream_t s);
 // tokens[i, 0:n_out] = out_tokens; tokens[i, n_out] = pred[i]   (mask_decoder.py:127-141)

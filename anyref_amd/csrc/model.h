@@ -51,6 +51,22 @@ class ModelBase {
                            float* logits, const int32_t* attn_q, float* attn_row) = 0;
   virtual void llm_extend(hipStream_t s, const float* embeds, const int32_t* pos0, const int32_t* lens, int B, int n,
                           float* hidden, float* logits) = 0;
+  // image sessions (anyref_session_*)
+  virtual void session_open(hipStream_t s, const float* clip_image, const float* sam_image, const int64_t* prefix_ids,
+                            int prefix_len, const int32_t* resized_hw, const int32_t* orig_hw) = 0;
+  virtual void session_generate(hipStream_t s, const int64_t* suffix_ids, const int32_t* lens, int Q, int Lmax,
+                                const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
+                                int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
+                                int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) = 0;
+  void session_close() {
+    sess_live_ = false;
+    sess_lost_by_ = nullptr;
+  }
+  // the entries that write what a session keeps on the device call this first (api.hip): the one flag, and who cleared it
+  void end_session(const char* by) {
+    if (sess_live_) sess_lost_by_ = by;
+    sess_live_ = false;
+  }
   virtual void project_audio(hipStream_t s, const float* audio_emb, int n, float* out) = 0;
   virtual void audio_encode(hipStream_t s, const float* mel, int n, float* emb) = 0;
   virtual void seg_tail(hipStream_t s, const float* sam_images, const int64_t* ids, const int32_t* ids_lens,
@@ -102,6 +118,12 @@ class ModelBase {
   std::vector<std::vector<int64_t>> draft_ids_;  // per row; empty: nothing pending
   std::vector<int> stat_offered_, stat_accepted_;  // of the last generate
   int stat_steps_ = 0, stat_passes_ = 0;
+  // the image session: row 0 of the KV cache / hidden states holds the prefix rows [0, sess_P_), image-embedding slot 0 the image
+  bool sess_live_ = false;
+  const char* sess_lost_by_ = nullptr;  // entry that ended the last session (for the error text)
+  int sess_P_ = 0, sess_rows_ = 0;      // spliced prefix rows; cache rows [0, sess_rows_) hold them
+  std::vector<int64_t> sess_prefix_;
+  int32_t sess_rhw_[2] = {0, 0}, sess_ohw_[2] = {0, 0};
   // hipGraph replay of the greedy decode step (default on)
   void set_graphs(bool on) { use_graphs_ = on; }
   // workgroup cap of the encoder's GEMM / attention launches while it co-runs with the decode loop (0 = uncapped)

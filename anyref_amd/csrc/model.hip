@@ -253,6 +253,12 @@ class Model : public ModelBase {
                 const int32_t* ref_pos, int B, int Lmax, int teacher, const float* hidden, int hidden_rows,
                 const float* attn_mean, const int32_t* resized_hw, const int32_t* orig_hw, int32_t* out_nseg,
                 float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets, float* out_low) override;
+  void session_open(hipStream_t s, const float* clip_image, const float* sam_image, const int64_t* prefix_ids, int prefix_len,
+                    const int32_t* resized_hw, const int32_t* orig_hw) override;
+  void session_generate(hipStream_t s, const int64_t* suffix_ids, const int32_t* lens, int nq, int Lmax,
+                        const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
+                        int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
+                        int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) override;
   void join_sam_public(hipStream_t s) { join_sam(s); }
 
  private:
@@ -484,7 +490,25 @@ class Model : public ModelBase {
   void run_tail(hipStream_t s, const float* sam_images, int B, const std::vector<int>& seg_b,
                 const std::vector<int>& seg_pos, const std::vector<int>& reph_s, const int32_t* resized_hw,
                 const int32_t* orig_hw, int32_t* out_nseg, float* out_masks, int64_t out_masks_cap,
-                int64_t* mask_offsets, float* out_low, const float* attn_given = nullptr, int attn_n = 0);
+                int64_t* mask_offsets, float* out_low, const float* attn_given = nullptr, int attn_n = 0,
+                bool one_image = false);
+  // generate() and session_generate() from "first token" to the end of the greedy loop: the lm_head pass on hidden row
+  // slen[b] - 1 of every sequence, then the draft-verified or the plain one-token loop (hipGraph step, EOS / ahead rules).
+  // `draft` is the call's (already taken) one-shot draft; fed / per_step: the encoder's CU share (generate only); early: early
+  // [SEG] masks may be queued (generate, batch 1), with the output pointers they write.  Fills gen[b] and the stat_ counters.
+  struct LoopArgs {
+    int max_new_tokens = 0, eos_token_id = -1;
+    bool keep_q = false, fed = false, early = false;
+    int per_step = 0;
+    const int32_t *resized_hw = nullptr, *orig_hw = nullptr;
+    float* out_masks = nullptr;
+    int64_t out_masks_cap = 0;
+    float* out_low = nullptr;
+  };
+  void decode_loop(hipStream_t s, int B, const std::vector<int>& slen, const std::vector<std::vector<int64_t>>& draft,
+                   const LoopArgs& la, std::vector<std::vector<int64_t>>& gen);
+  std::vector<int64_t> sess_ids_;  // host image of a session call's suffix ids (lives as long as the copy may read it)
+  std::vector<int32_t> sess_hw_;   // the session's sizes repeated per query (run_tail indexes them by row)
   void join_sam(hipStream_t s);
   // mask of a [SEG] the greedy loop has just emitted, on the side stream, while the loop goes on (generate, batch 1)
   void early_seg(hipEvent_t hidden_ready, int hidden_row, const int32_t* resized_hw, const int32_t* orig_hw,
@@ -2044,9 +2068,10 @@ template <typename T, typename TS>
 void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const std::vector<int>& seg_b,
                         const std::vector<int>& seg_pos, const std::vector<int>& reph_s, const int32_t* resized_hw,
                         const int32_t* orig_hw, int32_t* out_nseg, float* out_masks, int64_t out_masks_cap,
-                        int64_t* mask_offsets, float* out_low, const float* attn_given, int attn_n) {
+                        int64_t* mask_offsets, float* out_low, const float* attn_given, int attn_n, bool one_image) {
   // seg_b/seg_pos: (image, row of hidden_all_) of every [SEG]; reph_s: rephrase start row per image
   // attn_given (seg_tail only): caller's head-mean last-layer attention [B, attn_n, attn_n] instead of the K cache
+  // one_image (session_generate only): every row is about the image whose embedding sits in slot 0 of sam_emb_ already
   const anyref_config& c = cfg;
   const int H = c.llm_dim, S = c.llm_max_seq, nseg = (int)seg_b.size();
   // join BEFORE anything below can throw: a refused call must not leave the encoder running on the side stream
@@ -2105,7 +2130,7 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
   }
   gemmf(s, seg_h_, H, fc1_, seg_t_, H, nseg, ACT_RELU);
   gemmf(s, seg_t_, H, fc2_, pred_emb_, c.out_dim, nseg, ACT_NONE);
-  if (!sam_ready) sam_encoder(s, sam_images, B, sam_emb_);
+  if (!sam_ready && !one_image) sam_encoder(s, sam_images, B, sam_emb_);
   const int NK = sam_g_ * sam_g_, C = c.sam_out_chans, L = 4 * sam_g_;
   int row = 0;
   for (int b = 0; b < B; ++b) {
@@ -2115,7 +2140,7 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
     const int64_t hw = (int64_t)orig_hw[2 * b] * orig_hw[2 * b + 1];
     // seg rows of image b are contiguous because the host emits them image by image
     if (n > j0) {
-      mask_decoder(s, sam_emb_ + (size_t)b * NK * C, pred_emb_ + (size_t)(row + j0) * c.out_dim, n - j0, nullptr, nullptr);
+      mask_decoder(s, sam_emb_ + (one_image ? 0 : (size_t)b * NK * C), pred_emb_ + (size_t)(row + j0) * c.out_dim, n - j0, nullptr, nullptr);
       launch_postprocess(m_masks_, (int64_t)c.num_mask_tokens * L * L, n - j0, L, L, c.sam_img, resized_hw[2 * b],
                          resized_hw[2 * b + 1], orig_hw[2 * b], orig_hw[2 * b + 1], out_masks + mask_offsets[b] + j0 * hw,
                          s);
@@ -2204,6 +2229,59 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
   } else {
     fork_sam(s, sam_images, B);
   }
+  // early [SEG] masks: batch 1, encoder on the side stream, no rephrasing (that reads attention over the whole answer),
+  // no [SEG] inside the prompt (the tail's order is by position)
+  early_done_ = 0;
+  early_stop_ = false;
+  bool early = !early_off_ && sam_forked_ && B == 1 && c.rephrase_weight <= 0.f;
+  for (int i = 1; early && i < lens[0]; ++i)
+    if (input_ids[i] >= c.seg_lo && input_ids[i] <= c.seg_hi) early = false;
+  LoopArgs la;
+  la.max_new_tokens = max_new_tokens; la.eos_token_id = eos_token_id; la.keep_q = keep_q; la.fed = fed; la.early = early;
+  la.per_step = per_step; la.resized_hw = resized_hw; la.orig_hw = orig_hw; la.out_masks = out_masks;
+  la.out_masks_cap = out_masks_cap; la.out_low = out_low;
+  std::vector<std::vector<int64_t>> gen;
+  decode_loop(s, B, slen, draft, la, gen);
+  if (fed) sam_feed(nblk, false);  // the loop is over: what is left of the encoder has the chip to itself
+  const int Lout = Lmax + max_new_tokens;
+  std::vector<int> seg_b, seg_pos, reph(B, 0);
+  for (int b = 0; b < B; ++b) {
+    int64_t* row = out_ids + (size_t)b * Lout;
+    for (int i = 0; i < Lout; ++i) row[i] = 0;
+    for (int i = 0; i < lens[b]; ++i) row[i] = input_ids[(size_t)b * Lmax + i];
+    for (size_t i = 0; i < gen[b].size(); ++i) row[lens[b] + i] = gen[b][i];
+    out_lens[b] = lens[b] + (int)gen[b].size();
+    // [SEG] search in output_ids[:,1:] (anyref.py:723-726); hidden row = p + n_img - 1 (the "+255")
+    const int shift = img_pos[b] >= 0 ? n_img - 1 : 0;
+    for (int p = 0; p + 1 < out_lens[b]; ++p) {
+      const int64_t id = row[p + 1];
+      if (id >= c.seg_lo && id <= c.seg_hi) {
+        const int hp = p + shift;
+        if (hp >= slen[b] + (int)gen[b].size() - 1) continue;  // no hidden state past the last forward
+        seg_b.push_back(b);
+        seg_pos.push_back(hp);
+      }
+    }
+    reph[b] = lens[b] - 1 + shift;  // input_ids[i,1:].shape[0] + 255 (anyref.py:745)
+  }
+  run_tail(s, sam_images, B, seg_b, seg_pos, reph, resized_hw, orig_hw, out_nseg, out_masks, out_masks_cap,
+           mask_offsets, out_low);
+  if (out_hidden)
+    HIP_TRY(hipMemcpyAsync(out_hidden, hidden_all_, (size_t)B * S * H * 4, hipMemcpyDeviceToDevice, s));
+}
+
+// The part of a generating call between prefill and the masks (LoopArgs' note): generate() and session_generate() share it.
+template <typename T, typename TS>
+void Model<T, TS>::decode_loop(hipStream_t s, int B, const std::vector<int>& slen,
+                               const std::vector<std::vector<int64_t>>& draft, const LoopArgs& la,
+                               std::vector<std::vector<int64_t>>& gen) {
+  const anyref_config& c = cfg;
+  const int H = c.llm_dim, S = c.llm_max_seq, max_new_tokens = la.max_new_tokens, eos_token_id = la.eos_token_id;
+  const bool keep_q = la.keep_q, fed = la.fed, early = la.early;
+  const int per_step = la.per_step;
+  const int32_t *resized_hw = la.resized_hw, *orig_hw = la.orig_hw;
+  float *out_masks = la.out_masks, *out_low = la.out_low;
+  const int64_t out_masks_cap = la.out_masks_cap;
   // first token: logits of the last prompt row of every sequence
   {
     {
@@ -2227,20 +2305,13 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
                        rowmap_dev_, kvlen_dev_, s);
   }
   // greedy loop (HF greedy search: stop a row at EOS, pad finished rows; anyref.py:704-716)
-  std::vector<std::vector<int64_t>> gen(B);
+  gen.assign(B, std::vector<int64_t>());
   std::vector<char> fin(B, 0);
   // With an EOS id the host must see token k before it may queue step k + 1 (a step queued past the EOS would be a
   // whole wasted pass over the weights).  Without one (fixed-length generation) nothing depends on the token's
   // value: its copy and an event are queued, THEN the next step, and the host waits for the event while the device
   // already runs that step -- no host round trip between steps.
   const bool ahead = eos_token_id < 0;
-  // early [SEG] masks: batch 1, encoder on the side stream, no rephrasing (that reads attention over the whole answer),
-  // no [SEG] inside the prompt (the tail's order is by position)
-  early_done_ = 0;
-  early_stop_ = false;
-  bool early = !early_off_ && sam_forked_ && B == 1 && c.rephrase_weight <= 0.f;
-  for (int i = 1; early && i < lens[0]; ++i)
-    if (input_ids[i] >= c.seg_lo && input_ids[i] <= c.seg_hi) early = false;
   // a step runs beside the capped encoder while blocks are still being fed, and for one more step after the last feed
   // (the blocks queued during a step run at about half speed: through the step that follows)
   int corun_tail = 1;
@@ -2346,18 +2417,151 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
       if (fed) sam_feed(sam_next_blk_ + per_step, true);
     }
   }
-  if (fed) sam_feed(nblk, false);  // the loop is over: what is left of the encoder has the chip to itself
-  const int Lout = Lmax + max_new_tokens;
-  std::vector<int> seg_b, seg_pos, reph(B, 0);
-  for (int b = 0; b < B; ++b) {
+}
+
+// ---------------------------------------------------------------------------------------------
+// image sessions (anyref_session_*)
+// ---------------------------------------------------------------------------------------------
+template <typename T, typename TS>
+void Model<T, TS>::session_open(hipStream_t s, const float* clip_image, const float* sam_image, const int64_t* prefix_ids,
+                                int prefix_len, const int32_t* resized_hw, const int32_t* orig_hw) {
+  session_close();  // opening replaces the session; a refused open leaves none
+  HIP_TRY(hipSetDevice(device_));
+  const anyref_config& c = cfg;
+  if (!finalized_) throw std::runtime_error("session_open before finalize");
+  if (!clip_image || !sam_image || !prefix_ids || !resized_hw || !orig_hw) throw std::runtime_error("session_open: null argument");
+  if (prefix_len < 1 || prefix_ids[prefix_len - 1] != -200)
+    throw std::runtime_error("session_open: prefix_ids must end with the image placeholder (-200)");
+  for (int i = 0; i + 1 < prefix_len; ++i)
+    if (prefix_ids[i] == -200) throw std::runtime_error("session_open: more than one image placeholder in prefix_ids");
+  const int P = prefix_len + clip_n_ - 1;
+  if (P + 2 > c.llm_max_seq) throw std::runtime_error("session_open: the prefix leaves no room for a query in llm_max_seq");
+  early_done_ = 0;  // see forward_teacher
+  early_stop_ = false;
+  SamJoinGuard<Model<T, TS>> join_guard{this, s};
+  fork_sam(s, sam_image, 1);  // whole and uncapped on the side stream, beside the CLIP tower and the prefix prefill
+  clip_tower(s, clip_image, 1);
+  std::vector<int> slen, img_pos;
+  const int32_t len1 = prefix_len;
+  const int Sp = splice_inputs(s, prefix_ids, &len1, 1, prefix_len, nullptr, nullptr, 0, slen, img_pos);
+  if (Sp != P) throw std::runtime_error("internal: spliced prefix length");
+  llm_prefill(s, 1, P, slen_dev_, false);
+  if (!sam_forked_) sam_encoder(s, sam_image, 1, sam_emb_);  // overlap off: on the caller's stream
+  join_sam(s);
+  sess_P_ = P;
+  sess_rows_ = 1;
+  sess_prefix_.assign(prefix_ids, prefix_ids + prefix_len);
+  for (int i = 0; i < 2; ++i) {
+    sess_rhw_[i] = resized_hw[i];
+    sess_ohw_[i] = orig_hw[i];
+  }
+  sess_live_ = true;
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, const int32_t* lens, int nq, int Lmax,
+                                    const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
+                                    int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg,
+                                    float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets, float* out_low,
+                                    float* out_hidden) {
+  // the one-shot draft is taken here, as in generate(): whatever happens below, nothing stays armed
+  std::vector<std::vector<int64_t>> draft;
+  draft.swap(draft_ids_);
+  HIP_TRY(hipSetDevice(device_));
+  const anyref_config& c = cfg;
+  stat_offered_.assign(nq > 0 ? nq : 0, 0);
+  stat_accepted_.assign(nq > 0 ? nq : 0, 0);
+  stat_steps_ = stat_passes_ = 0;
+  // ---- everything that can refuse the call, before anything is queued ----
+  if (!sess_live_) {
+    if (sess_lost_by_) throw std::runtime_error(std::string("session lost: ended by ") + sess_lost_by_);
+    throw std::runtime_error("no session open (anyref_session_open)");
+  }
+  if (nq < 1 || nq > c.max_batch) throw std::runtime_error("session_generate: queries outside [1, max_batch]");
+  if (max_new_tokens < 1) throw std::runtime_error("max_new_tokens must be >= 1");
+  if (c.rephrase_weight > 0.f)
+    throw std::runtime_error("session_generate: rephrase_weight > 0 is not served inside a session (rephrasing reads the last "
+                             "layer's queries of the whole prompt, which the extend path does not keep)");
+  if (!suffix_ids || !lens || !out_ids || !out_lens || !out_nseg || !mask_offsets) throw std::runtime_error("session_generate: null argument");
+  if (!draft.empty() && (int)draft.size() != nq) throw std::runtime_error("the pending draft was set for another batch size");
+  const int H = c.llm_dim, S = c.llm_max_seq, n_img = clip_n_, P = sess_P_, np = (int)sess_prefix_.size();
+  int n = 0;
+  for (int b = 0; b < nq; ++b) {
+    if (lens[b] < 1 || lens[b] > Lmax) throw std::runtime_error("session_generate: suffix length outside [1, Lmax]");
+    if (P + lens[b] + max_new_tokens > S) throw std::runtime_error("session_generate: prefix + suffix + max_new_tokens exceeds llm_max_seq");
+    n = std::max(n, lens[b]);
+  }
+  if (n_extra < 0 || (n_extra > 0 && (!extra_embeds || !extra_slots))) throw std::runtime_error("session_generate: bad extra rows");
+  if (n_extra > (int)c.max_batch * std::max(c.max_seg, 64)) throw std::runtime_error("too many extra slots");
+  std::vector<char> replaced((size_t)nq * n, 0);
+  for (int i = 0; i < n_extra; ++i) {
+    const int b = extra_slots[2 * i], p = extra_slots[2 * i + 1];
+    if (b < 0 || b >= nq || p < 0 || p >= lens[b]) throw std::runtime_error("extra slot out of range");
+    replaced[(size_t)b * n + p] = 1;
+  }
+  sess_ids_.assign((size_t)nq * n, 0);  // compact [nq, n]; padding and replaced rows embed id 0 (never read / overwritten)
+  for (int b = 0; b < nq; ++b)
+    for (int i = 0; i < lens[b]; ++i) {
+      const int64_t id = suffix_ids[(size_t)b * Lmax + i];
+      if (id == -200) throw std::runtime_error("session_generate: image placeholder inside a suffix");
+      if (id >= 0 && id < c.llm_vocab) sess_ids_[(size_t)b * n + i] = id;
+      else if (!replaced[(size_t)b * n + i]) throw std::runtime_error("session_generate: a suffix id outside the vocabulary has no extra row");
+    }
+  std::vector<int> slen(nq), pos0(nq, P);
+  for (int b = 0; b < nq; ++b) slen[b] = P + lens[b];
+  early_done_ = 0;  // see forward_teacher
+  early_stop_ = false;
+  // ---- 1. the prefix for cache rows that do not hold it yet: K, V of every layer in one launch, the hidden rows in another ----
+  if (nq > sess_rows_) {
+    constexpr int64_t kv_elem = sizeof(Q);  // the cache element (the class's type Q: f32 in the parity modes, 16-bit in perf)
+    static_assert(kv_elem == sizeof(*kcache_), "the broadcast is sized by the cache element");
+    launch_kv_broadcast(kcache_, c.llm_layers, vcache_, c.llm_layers, (int64_t)cache_layer_stride_ * kv_elem, c.max_batch, S,
+                        (int64_t)H * kv_elem, P, sess_rows_, nq, s);
+    launch_kv_broadcast(hidden_all_, 1, nullptr, 0, (int64_t)c.max_batch * S * H * 4, c.max_batch, S, (int64_t)H * 4, P, sess_rows_,
+                        nq, s);
+    sess_rows_ = nq;
+  }
+  // ---- 2. the suffix rows' embeddings, compact [nq, n, H] ----
+  HIP_TRY(hipMemcpyAsync(ids_dev_, sess_ids_.data(), (size_t)nq * n * 8, hipMemcpyHostToDevice, s));
+  launch_embed_rows(ids_dev_, nq * n, emb_table_, kEmbDtype, H, l_x_, s);
+  if (extra_ev_) {  // extra_embeds queued on another stream (anyref_set_extra_event)
+    hipEvent_t ev = reinterpret_cast<hipEvent_t>(extra_ev_);
+    extra_ev_ = nullptr;
+    HIP_TRY(hipStreamWaitEvent(s, ev, 0));
+  }
+  if (n_extra > 0) {
+    {
+      StageScope stage_scope(this, ST_EXTRA, s);
+      int *eb = stage_extra_, *ep = stage_extra_ + n_extra;
+      for (int i = 0; i < n_extra; ++i) {
+        eb[i] = extra_slots[2 * i];
+        ep[i] = extra_slots[2 * i + 1];
+      }
+      HIP_TRY(hipMemcpyAsync(idx_a_, eb, n_extra * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(idx_b_, ep, n_extra * 4, hipMemcpyHostToDevice, s));
+    }
+    launch_scatter_rows(extra_embeds, idx_a_, idx_b_, n_extra, l_x_, n, H, s);
+  }
+  // ---- 3, 4. the extend pass: n rows per query behind the prefix ----
+  PrefillExt e;
+  ext_upload(s, pos0.data(), lens, nq, n, e);
+  llm_prefill(s, nq, n, e.lens, false, &e);
+  // ---- 5, 6. first token and the greedy loop ----
+  LoopArgs la;
+  la.max_new_tokens = max_new_tokens; la.eos_token_id = eos_token_id;
+  std::vector<std::vector<int64_t>> gen;
+  decode_loop(s, nq, slen, draft, la, gen);
+  // ---- 7. ids and masks: generate()'s arithmetic on prefix + suffix + answer, every row about the one image ----
+  const int Lout = np + Lmax + max_new_tokens, shift = n_img - 1;
+  std::vector<int> seg_b, seg_pos, reph(nq, 0);
+  for (int b = 0; b < nq; ++b) {
     int64_t* row = out_ids + (size_t)b * Lout;
     for (int i = 0; i < Lout; ++i) row[i] = 0;
-    for (int i = 0; i < lens[b]; ++i) row[i] = input_ids[(size_t)b * Lmax + i];
-    for (size_t i = 0; i < gen[b].size(); ++i) row[lens[b] + i] = gen[b][i];
-    out_lens[b] = lens[b] + (int)gen[b].size();
-    // [SEG] search in output_ids[:,1:] (anyref.py:723-726); hidden row = p + n_img - 1 (the "+255")
-    const int shift = img_pos[b] >= 0 ? n_img - 1 : 0;
-    for (int p = 0; p + 1 < out_lens[b]; ++p) {
+    for (int i = 0; i < np; ++i) row[i] = sess_prefix_[i];
+    for (int i = 0; i < lens[b]; ++i) row[np + i] = suffix_ids[(size_t)b * Lmax + i];
+    for (size_t i = 0; i < gen[b].size(); ++i) row[np + lens[b] + i] = gen[b][i];
+    out_lens[b] = np + lens[b] + (int)gen[b].size();
+    for (int p = 0; p + 1 < out_lens[b]; ++p) {  // [SEG] search in output_ids[:,1:], hidden row p + n_img - 1
       const int64_t id = row[p + 1];
       if (id >= c.seg_lo && id <= c.seg_hi) {
         const int hp = p + shift;
@@ -2366,12 +2570,17 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
         seg_pos.push_back(hp);
       }
     }
-    reph[b] = lens[b] - 1 + shift;  // input_ids[i,1:].shape[0] + 255 (anyref.py:745)
   }
-  run_tail(s, sam_images, B, seg_b, seg_pos, reph, resized_hw, orig_hw, out_nseg, out_masks, out_masks_cap,
-           mask_offsets, out_low);
+  sess_hw_.resize((size_t)4 * nq);
+  for (int b = 0; b < nq; ++b)
+    for (int i = 0; i < 2; ++i) {
+      sess_hw_[2 * b + i] = sess_rhw_[i];
+      sess_hw_[2 * nq + 2 * b + i] = sess_ohw_[i];
+    }
+  run_tail(s, nullptr, nq, seg_b, seg_pos, reph, sess_hw_.data(), sess_hw_.data() + 2 * nq, out_nseg, out_masks, out_masks_cap,
+           mask_offsets, out_low, nullptr, 0, true);
   if (out_hidden)
-    HIP_TRY(hipMemcpyAsync(out_hidden, hidden_all_, (size_t)B * S * H * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(out_hidden, hidden_all_, (size_t)nq * S * H * 4, hipMemcpyDeviceToDevice, s));
 }
 
 template <typename T, typename TS>

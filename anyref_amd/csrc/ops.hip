@@ -978,6 +978,55 @@ void launch_embed_rows(const int64_t* ids, int B, const void* table, int dtype, 
                        hipStream_t s) {
   hipLaunchKernelGGL(embed_rows_kernel, dim3(B), dim3(256), 0, s, ids, table, dtype, D, x);
 }
+// Prefix broadcast (image sessions): one workgroup column per plane (blockIdx.y), grid-stride over the plane's prefix in pieces
+// of V; a piece is loaded once and stored to every target row, four pieces in flight per thread.
+template <typename V>
+__global__ void kv_broadcast_kernel(char* __restrict__ base0, int planes0, char* __restrict__ base1, int64_t plane_stride,
+                                    int64_t row_stride, int64_t nvec, int r0, int r1) {
+  const int plane = blockIdx.y;
+  char* base = plane < planes0 ? base0 + (int64_t)plane * plane_stride : base1 + (int64_t)(plane - planes0) * plane_stride;
+  const V* __restrict__ src = reinterpret_cast<const V*>(base);
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + 3 * step < nvec; i += 4 * step) {
+    const V a = src[i], b = src[i + step], c = src[i + 2 * step], d = src[i + 3 * step];
+    for (int r = r0; r < r1; ++r) {
+      V* dst = reinterpret_cast<V*>(base + (int64_t)r * row_stride);
+      dst[i] = a; dst[i + step] = b; dst[i + 2 * step] = c; dst[i + 3 * step] = d;
+    }
+  }
+  for (; i < nvec; i += step) {
+    const V a = src[i];
+    for (int r = r0; r < r1; ++r) reinterpret_cast<V*>(base + (int64_t)r * row_stride)[i] = a;
+  }
+}
+void launch_kv_broadcast(void* base0, int planes0, void* base1, int planes1, int64_t plane_stride, int rows, int maxS,
+                         int64_t row_bytes, int P, int r0, int r1, hipStream_t s) {
+  if (!base0 || planes0 < 1 || planes1 < 0 || (planes1 > 0 && !base1) || rows < 1 || maxS < 1 || row_bytes < 2 || (row_bytes & 1))
+    throw std::runtime_error("kv_broadcast: bad buffer description");
+  if (P < 0 || P > maxS) throw std::runtime_error("kv_broadcast: P outside [0, maxS]");
+  if (r0 < 1 || r1 > rows) throw std::runtime_error("kv_broadcast: target rows outside [1, rows]");
+  const int64_t row_stride = (int64_t)maxS * row_bytes;
+  if (plane_stride < (int64_t)rows * row_stride && planes0 + planes1 > 1)
+    throw std::runtime_error("kv_broadcast: planes overlap");
+  if (P == 0 || r1 <= r0) return;
+  const int planes = planes0 + planes1;
+  const int64_t bytes = (int64_t)P * row_bytes;
+  const bool v16 = row_bytes % 16 == 0 && plane_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(base0) & 15) == 0 &&
+                   (planes1 == 0 || (reinterpret_cast<uintptr_t>(base1) & 15) == 0);
+  const int64_t nvec = bytes / (v16 ? 16 : 2);
+  // grid sized to the bytes: one thread per four pieces, capped at about 2048 workgroups over all planes (the rest is the
+  // grid-stride loop)
+  const int64_t want = (nvec + 4 * 256 - 1) / (4 * 256);
+  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, std::max(1, 2048 / planes)));
+  dim3 grid(gx, planes);
+  if (v16)
+    hipLaunchKernelGGL(kv_broadcast_kernel<uint4>, grid, dim3(256), 0, s, (char*)base0, planes0, (char*)base1, plane_stride,
+                       row_stride, nvec, r0, r1);
+  else
+    hipLaunchKernelGGL(kv_broadcast_kernel<unsigned short>, grid, dim3(256), 0, s, (char*)base0, planes0, (char*)base1,
+                       plane_stride, row_stride, nvec, r0, r1);
+}
 __global__ void decode_index_kernel(const int* __restrict__ pos, int B, int maxS, int* __restrict__ row_map,
                                     int* __restrict__ kvlen) {
   const int b = threadIdx.x;

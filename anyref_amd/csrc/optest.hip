@@ -340,6 +340,18 @@ int anyref_op_draft_accept(void* stream, const float* logits, int B, int k, int 
   });
 }
 
+int anyref_op_kv_broadcast(void* stream, void* kc, void* vc, int layers, int rows, int maxS, int row_elems, int elem_size,
+                           int P, int r0, int r1) {
+  OP_GUARD({
+    if (!kc) throw std::runtime_error("op_kv_broadcast: null argument");
+    if (elem_size != 2 && elem_size != 4) throw std::runtime_error("op_kv_broadcast: elem_size 2 / 4");
+    if (layers < 1 || rows < 1 || maxS < 1 || row_elems < 1) throw std::runtime_error("op_kv_broadcast: bad shape");
+    const int64_t row_bytes = (int64_t)row_elems * elem_size;
+    launch_kv_broadcast(kc, layers, vc, vc ? layers : 0, (int64_t)rows * maxS * row_bytes, rows, maxS, row_bytes, P, r0, r1,
+                        (hipStream_t)stream);
+  });
+}
+
 int anyref_op_norm(int t, void* stream, const float* x, const float* gain, const float* bias, float* y, int M,
                    int D, float eps, int rms) {
   OP_GUARD({

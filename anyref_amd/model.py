@@ -68,7 +68,7 @@ def _c_config(cfg: AnyRefConfig, mode: int, max_batch: int, max_seg: int) -> _li
 _NEEDS_HANDLE = frozenset({
     "generate", "model_forward_new", "forward", "__call__", "encode_images", "sam_encode", "mask_decode", "llm_forward",
     "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
-    "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats"})
+    "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session"})
 
 
 class AnyRefForCausalLM:
@@ -751,6 +751,14 @@ class AnyRefForCausalLM:
             _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)), "generate")
         if self._draft_policy == "last":
             self._last_answers = [out_ids[b, int(lens[b]): int(out_lens[b])].tolist() for b in range(B)]
+        res = self._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width)
+        if _return_extras:
+            return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **self.draft_stats(B))
+        return res
+
+    def _result(self, out_ids, out_lens, out_nseg, offs, out_masks, height, width):
+        """what `generate` returns, from the buffers anyref_generate / anyref_session_generate filled"""
+        B = out_ids.shape[0]
         # HF pads finished rows with pad_token_id
         full = torch.full((B, int(out_lens.max())), int(self.config.pad_token_id or 0), dtype=torch.long)
         for b in range(B):
@@ -774,9 +782,21 @@ class AnyRefForCausalLM:
             res = (output_ids, pred_masks, (None, None, None))
         if self.success_arity == 2 and res[1] is not None and not (self.cfg.rephrase_weight > 0 and total < B):
             res = res[:2]                                 # the reference's own success path (anyref.py:822): any [SEG], no `no_mask`
-        if _return_extras:
-            return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **self.draft_stats(B))
         return res
+
+    def image_session(self, clip_image, sam_image, sam_resized_size, height, width, prefix_ids) -> "ImageSession":
+        """Encode one image once and answer many queries behind its cache (`anyref_session_open`): the CLIP
+        tower, the SAM encoder and the prefill of `prefix_ids` -- the start every prompt about this image shares, up to and
+        including the image placeholder -- run here; `sess.generate(...)` then costs the suffix and the answer only.
+
+            with model.image_session(clip, sam, resized, h, w, ids[: image_pos + 1]) as sess:
+                for ids in prompts_about_this_image:
+                    out_ids, masks, _ = sess.generate(ids, max_new_tokens=...)
+
+        clip_image [3, S, S] or [1, 3, S, S]; sam_resized_size (h, w) and height / width of the one image (one-element lists as
+        `generate` takes them are accepted).  One session per model: opening another replaces it, and any other call that runs
+        the model (`generate`, `forward`, `llm_forward`, `encode_images`, ...) ends it."""
+        return ImageSession(self, clip_image, sam_image, sam_resized_size, height, width, prefix_ids)
 
     def forward(self, **kwargs):
         """`AnyRefForCausalLM.forward` (anyref.py:233-237): dispatch as the reference does."""
@@ -858,6 +878,102 @@ class AnyRefForCausalLM:
         if _return_extras:
             out.update(pred_masks=pred_masks, hidden=hid, logits=logits)
         return out
+
+
+def _flat_ints(v):
+    """ints of a scalar / list / tuple / tensor, flattened (a one-element list as `generate` takes it, or the bare value)"""
+    return [int(x) for x in torch.as_tensor(v).reshape(-1).tolist()]
+
+
+class ImageSession:
+    """`AnyRefForCausalLM.image_session(...)`: a context manager around `anyref_session_open` / `_generate` / `_close`."""
+
+    def __init__(self, model: AnyRefForCausalLM, clip_image, sam_image, sam_resized_size, height, width, prefix_ids):
+        from .session import check_prefix
+        self.model = m = model
+        self.prefix = check_prefix(prefix_ids.tolist() if hasattr(prefix_ids, "tolist") else prefix_ids)
+        clip = clip_image.to(m.device, torch.float32).contiguous()
+        sam = sam_image.to(m.device, torch.float32).contiguous()
+        if clip.numel() != 3 * m.cfg.clip.image_size ** 2 or sam.numel() != 3 * m.cfg.sam.img_size ** 2:
+            raise ValueError("an image session holds exactly one image: clip_image [3, S, S] and sam_image [3, S, S]")
+        rs, hh, ww = _flat_ints(sam_resized_size), _flat_ints(height), _flat_ints(width)
+        if len(rs) != 2 or len(hh) != 1 or len(ww) != 1:
+            raise ValueError("an image session holds exactly one image: one (h, w) resized size, one height, one width")
+        self.height, self.width = hh[0], ww[0]
+        rs_t = torch.tensor(rs, dtype=torch.int32)
+        os_t = torch.tensor([self.height, self.width], dtype=torch.int32)
+        pre = torch.tensor(self.prefix, dtype=torch.long)
+        m._check(m.lib.anyref_session_open(m.h, m._stream(), _ptr(clip), _ptr(sam), _ptr(pre), len(self.prefix), _ptr(rs_t),
+                                           _ptr(os_t)), "session_open")
+        self.open = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        if self.open and self.model.h:
+            self.model._check(self.model.lib.anyref_session_close(self.model.h), "session_close")
+        self.open = False
+
+    @torch.no_grad()
+    def generate(self, input_ids, audios=None, ref_images=None, max_new_tokens=128, attention_masks=None, draft_ids=None,
+                 _return_extras: bool = False):
+        """`model.generate` for Q <= max_batch queries about the session's image, same return shape; the Q-row answer is what Q
+        plain calls on the full prompts return.  A row of `input_ids` is either a suffix (what follows the image placeholder) or
+        a full prompt as the reference's data loader produces it, which must begin with the session's prefix and is cut there;
+        a row that does not raises ValueError naming the row (anyref_amd/session.py).  `output_ids` are full rows: prefix +
+        suffix + answer.  `audios` positions are looked up in the suffixes.  `draft_ids` as in `model.generate`;
+        `set_draft_policy("last")` is NOT applied inside a session (consecutive queries about one image have different answers
+        more often than consecutive images have).  `ref_images` is not served: its features come out of the CLIP tower
+        (`encode_images`), a call that ends the session."""
+        from .draft import normalize_drafts
+        from .session import cut_rows
+        m = self.model
+        if not self.open:
+            raise RuntimeError("session_generate: this image session was closed")
+        if ref_images is not None:
+            raise NotImplementedError("ref_images inside an image session: encode_images would end the session")
+        ids, lens = m._rows(input_ids, attention_masks)
+        suffixes = cut_rows([ids[b, : int(lens[b])].tolist() for b in range(ids.shape[0])], self.prefix)
+        Q, Lmax = len(suffixes), max(len(r) for r in suffixes)
+        if Q > m.max_batch:
+            raise ValueError(f"batch {Q} > max_batch {m.max_batch} the handle was created for")
+        suf = torch.zeros(Q, Lmax, dtype=torch.long)
+        for b, r in enumerate(suffixes):
+            suf[b, : len(r)] = torch.tensor(r, dtype=torch.long)
+        slens = torch.tensor([len(r) for r in suffixes], dtype=torch.int32)
+        extra, slots, n_extra = m._extra(suf, slens, audios, None)
+        Lout = len(self.prefix) + Lmax + int(max_new_tokens)
+        out_ids = torch.zeros(Q, Lout, dtype=torch.long)
+        out_lens = torch.zeros(Q, dtype=torch.int32)
+        out_nseg = torch.zeros(Q, dtype=torch.int32)
+        offs = torch.zeros(Q, dtype=torch.long)
+        height, width = [self.height] * Q, [self.width] * Q
+        cap = Q * m.max_seg * self.height * self.width
+        out_masks = torch.empty(cap, device=m.device, dtype=torch.float32)
+        out_low = hid = None
+        if _return_extras:
+            L = 4 * m.cfg.sam.grid
+            out_low = torch.zeros(Q, m.max_seg, L, L, device=m.device, dtype=torch.float32)
+            if _return_extras != "low":
+                hid = torch.empty(Q, m.cfg.llm.max_seq, m.cfg.llm.dim, device=m.device, dtype=torch.float32)
+        eos = m.config.eos_token_id if m.config.eos_token_id is not None else -1
+        if draft_ids is not None:
+            drafts = normalize_drafts(draft_ids, Q)
+            if any(drafts):
+                m.set_draft(drafts)
+        m._check(m.lib.anyref_session_generate(
+            m.h, m._stream(), _ptr(suf), _ptr(slens), Q, Lmax, _ptr(extra), _ptr(slots), n_extra, int(max_new_tokens), int(eos),
+            _ptr(out_ids), _ptr(out_lens), _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)),
+            "session_generate")
+        res = m._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width)
+        if _return_extras:
+            return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **m.draft_stats(Q))
+        return res
 
 
 def dice_loss(inputs, targets, num_masks, scale=1000, eps=1e-6):

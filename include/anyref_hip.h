@@ -270,6 +270,51 @@ int anyref_set_draft(anyref_handle* h, const int64_t* draft_ids, const int32_t* 
 int anyref_draft_stats(anyref_handle* h, int32_t* offered, int32_t* accepted, int B, int32_t* decode_steps,
                        int32_t* verify_passes);
 
+/*
+ * Image sessions: the callers' loops ask several questions about one image (RefCOCO: ~7 expressions per image,
+ * one `generate` each with the same clip_images / sam_images, eval_referseg.py:124-137).  Everything that depends only on the
+ * image -- CLIP tower + projector, SAM encoder, the prefill of `system prompt + image tokens` -- is done once by
+ * anyref_session_open; anyref_session_generate then prefills only each query's suffix behind that cache (anyref_llm_extend's
+ * path) and decodes.  One session per handle; opening again replaces it.
+ *
+ *   clip_image f32 [1,3,clip_image,clip_image] dev, sam_image f32 [1,3,sam_img,sam_img] dev
+ *   prefix_ids i64 [prefix_len] host: the start of every prompt, up to and INCLUDING the image placeholder (-200), which must be
+ *              its last id and occur exactly once
+ *   resized_hw / orig_hw i32 [2] host, as one row of anyref_generate's
+ * Runs the CLIP tower and projector, the SAM encoder (on the side stream unless overlap is off; joined before the call returns
+ * its work to `stream`) into image-embedding slot 0, and the ordinary prefill of the P = prefix_len + n_patches - 1 spliced
+ * prefix rows into row 0 of the KV cache and of the hidden states.  Error if P + 2 > llm_max_seq.
+ */
+int anyref_session_open(anyref_handle* h, void* stream, const float* clip_image, const float* sam_image,
+                        const int64_t* prefix_ids, int prefix_len, const int32_t* resized_hw, const int32_t* orig_hw);
+/*
+ * Q queries (1 <= Q <= max_batch) about the session's image in one call: a Q-row answer equals Q anyref_generate calls of one
+ * row each on prefix_ids + suffix.
+ *   suffix_ids i64 [Q, Lmax] host, lens i32 [Q] host (>= 1): what follows the placeholder in each prompt
+ *   extra_embeds / extra_slots as anyref_generate, slot = (query, position in suffix_ids); a suffix id outside [0, vocab)
+ *              must have an extra row
+ *   out_ids   i64 [Q, prefix_len + Lmax + max_new_tokens] host: prefix_ids + suffix + new tokens; out_lens counts all three
+ *   out_nseg, out_masks, out_masks_cap, mask_offsets, out_low, out_hidden: as anyref_generate for a batch of Q (every query
+ *              has the session's image and sizes; hidden rows [0, P) of every query are the prefix's)
+ * Cache rows 1 .. Q-1 receive the prefix by one copy launch (anyref_op_kv_broadcast; rows that already hold this session's
+ * prefix are skipped: queries only ever write positions >= P), the suffix rows run as anyref_llm_extend's pass at pos0 = P, then
+ * the greedy loop of anyref_generate (hipGraph step, EOS rules) and its masks, all after the loop: no encoder co-runs, so the
+ * CU share and early masks do not apply.  A pending anyref_set_draft is honoured under the rules stated there with
+ * slen[b] = P + lens[b], one-shot and consumed by this call whatever happens; anyref_draft_stats reports the call's counters.
+ * Refused before anything is queued, the session staying usable: P + lens[b] + max_new_tokens > llm_max_seq, lens[b] < 1, Q
+ * outside [1, max_batch], an image placeholder inside a suffix, and rephrase_weight > 0 (rephrasing reads the last layer's
+ * queries of the whole prompt, which the extend path does not keep -- as a draft is ignored under rephrasing).
+ * Any other entry that writes row 0 of the KV cache or of the hidden states, the CLIP feature buffer or image-embedding slot 0
+ * ends the session: anyref_generate, anyref_forward_teacher, anyref_llm_forward, anyref_llm_extend, anyref_seg_tail,
+ * anyref_encode_images, anyref_finalize.  The next anyref_session_generate then fails with "session lost: ended by <entry>".
+ */
+int anyref_session_generate(anyref_handle* h, void* stream, const int64_t* suffix_ids, const int32_t* lens, int Q, int Lmax,
+                            const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
+                            int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
+                            int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden);
+/* Forget the session (anyref_destroy does the same).  No error if none is open. */
+int anyref_session_close(anyref_handle* h);
+
 /* hipGraph replay of the greedy decode step (default 1): one step is ~170 launches with fixed
  * arguments (position / next token live on the device), captured once per batch size.  0 launches
  * them eagerly; the per-kernel profiler below always runs eagerly. */

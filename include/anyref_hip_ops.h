@@ -59,6 +59,13 @@ int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_
 int anyref_op_draft_accept(void* stream, const float* logits, int B, int k, int N, int ldx, int64_t* p, const int64_t* draft,
                            const int32_t* draft_lens, int64_t* next, int32_t* pos, int64_t* tokens, int32_t* accepted,
                            const void* table, int dtype, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen);
+/* prefix broadcast of an image session (anyref_session_generate): kc and vc (vc may be NULL: one buffer) are KV caches
+ * [layers][rows][maxS][row_elems] of elements of elem_size bytes (2 or 4; the kernel moves bytes and never interprets them).
+ * In every layer of both, positions [0, P) of row 0 are copied to rows [r0, r1); everything else is left as it was.  One launch
+ * for all layers, both buffers and all target rows.  P == 0 or r1 <= r0 (a single query) launches nothing and returns 0.
+ * Error if P > maxS, r0 < 1 or r1 > rows. */
+int anyref_op_kv_broadcast(void* stream, void* kc, void* vc, int layers, int rows, int maxS, int row_elems, int elem_size,
+                           int P, int r0, int r1);
 /* LayerNorm (rms=0) / RMSNorm (rms=1); x f32, y f32 */
 int anyref_op_norm(int t, void* stream, const float* x, const float* gain, const float* bias, float* y, int M,
                    int D, float eps, int rms);
