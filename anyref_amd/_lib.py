@@ -104,6 +104,8 @@ SYMBOLS = {
     "anyref_set_seg_range": (_I, [_P, _I, _I]),
     "anyref_set_overlap": (_I, [_P, _I]),
     "anyref_set_early_tail": (_I, [_P, _I]),
+    "anyref_early_masks_done": (_I, [_P]),
+    "anyref_set_rephrase_paths": (_I, [_P, _I]),
     "anyref_set_extra_event": (_I, [_P, _P]),
     "anyref_set_graphs": (_I, [_P, _I]),
     "anyref_set_side_share": (_I, [_P, _I, _I]),
@@ -143,6 +145,8 @@ SYMBOLS = {
     "anyref_op_split_roundtrip": (_I, [_I, _P, _P, _P, _P, _I, _I]),
     "anyref_op_rope_table": (_I, [_I, _I, _F, _P]),
     "anyref_op_decode_attn": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _I]),
+    "anyref_op_seg_rephrase": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _F, _F, _P, _P]),
+    "anyref_op_rephrase_chain": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _F, _F, _P]),
     "anyref_op_rope_cache": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "anyref_op_argmax": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_draft_accept": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),

@@ -161,6 +161,8 @@ int anyref_set_seg_range(anyref_handle* h, int lo, int hi) { GUARD(h, h->m->set_
 
 int anyref_set_overlap(anyref_handle* h, int on) { GUARD(h, h->m->set_overlap(on != 0)); }
 int anyref_set_early_tail(anyref_handle* h, int on) { GUARD(h, h->m->set_early_tail(on != 0)); }
+int anyref_early_masks_done(anyref_handle* h) { return h && h->m ? h->m->early_masks_done() : 0; }
+int anyref_set_rephrase_paths(anyref_handle* h, int on) { GUARD(h, h->m->set_rephrase_paths(on != 0)); }
 int anyref_set_extra_event(anyref_handle* h, void* event) { GUARD(h, h->m->set_extra_event(event)); }
 
 int anyref_set_graphs(anyref_handle* h, int on) { GUARD(h, h->m->set_graphs(on != 0)); }

@@ -1654,6 +1654,133 @@ template void launch_attn_row_mean<f16>(const void*, int64_t, int64_t, const voi
                                         const int*, int, int, int, float, float*, int, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
+// Rephrase branch, pass A (launch_seg_rephrase in kernels.h): the softmax row of ONE query per (head, item)
+// workgroup, written for the span [s0, e0) only.  The key rows [0, e0] are read once, 16 bytes per lane: the lpr = hd *
+// sizeof(Q) / 16 adjacent lanes that share a key row add their partial dots by __shfl_xor, the scaled scores stay in LDS
+// (maxS floats), max and sum go over the workgroup in a fixed order.  Four key rows per lane group are in flight.
+// ---------------------------------------------------------------------------------------------
+namespace {
+template <typename Q>
+__device__ inline void load_piece16(const Q* p, float (&v)[16 / sizeof(Q)]);
+template <>
+__device__ inline void load_piece16<float>(const float* p, float (&v)[4]) {
+  const float4 u = *reinterpret_cast<const float4*>(p);
+  v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
+}
+template <>
+__device__ inline void load_piece16<bf16>(const bf16* p, float (&v)[8]) {
+  const uint4 u = *reinterpret_cast<const uint4*>(p);
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = __builtin_bit_cast(float, w[i] << 16);
+    v[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
+  }
+}
+template <>
+__device__ inline void load_piece16<f16>(const f16* p, float (&v)[8]) {
+  const uint4 u = *reinterpret_cast<const uint4*>(p);
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[i] & 0xffffu));
+    v[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[i] >> 16));
+  }
+}
+}  // namespace
+template <typename Q>
+__global__ __launch_bounds__(256) void seg_attn_span_kernel(const Q* __restrict__ qk, const Q* __restrict__ K, int maxS,
+                                                            int heads, int hd, int lpr, const int* __restrict__ items,
+                                                            int span_cap, float scale, float* __restrict__ scratch) {
+  constexpr int N = 16 / sizeof(Q);  // elements of a 16-byte piece
+  constexpr int U = 4;               // key rows per lane group in flight
+  extern __shared__ float seg_sc[];  // [maxS] scores, then exp(score - max); [8] wave maxima and sums
+  const int h = blockIdx.x, it = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = items[4 * it], e0 = items[4 * it + 1], s0 = items[4 * it + 2];
+  if (s0 < 0 || e0 <= s0 || e0 >= maxS || e0 - s0 > span_cap) return;  // (the same for every thread)
+  float* red = seg_sc + maxS;
+  const int n = e0 + 1, piece = tid % lpr, grp = tid / lpr, rows = 256 / lpr;
+  const int64_t row = (int64_t)heads * hd;
+  float qv[N];
+  load_piece16<Q>(qk + ((int64_t)b * maxS + e0) * row + (int64_t)h * hd + piece * N, qv);
+  const Q* kb = K + (int64_t)b * maxS * row + (int64_t)h * hd + piece * N;
+  for (int j0 = grp; j0 < n; j0 += U * rows) {
+    float kv[U][N];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * rows;
+      if (j < n) {
+        load_piece16<Q>(kb + (int64_t)j * row, kv[u]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) kv[u][i] = 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < N; ++i) s = fmaf(qv[i], kv[u][i], s);
+      for (int o = lpr >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);  // the lanes of one key row (j is theirs alike)
+      const int j = j0 + u * rows;
+      if (piece == 0 && j < n) seg_sc[j] = s * scale;
+    }
+  }
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int j = tid; j < n; j += 256) mx = fmaxf(mx, seg_sc[j]);
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sum = 0.f;
+  for (int j = tid; j < n; j += 256) {
+    const float e = expf(seg_sc[j] - mx);
+    seg_sc[j] = e;
+    sum += e;
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = (red[4] + red[5]) + (red[6] + red[7]);
+  float* o = scratch + ((int64_t)it * heads + h) * span_cap;
+  for (int j = s0 + tid; j < e0; j += 256) o[j - s0] = seg_sc[j] / sum;
+}
+template <typename Q>
+void launch_seg_attn_span(const void* q_keep, const void* kc, int maxS, int heads, int hd, const int* items, int n_items,
+                          int span_cap, float scale, float* scratch, hipStream_t s) {
+  if (n_items <= 0) return;
+  if (!seg_rephrase_shape_ok((int)sizeof(Q), hd, maxS, span_cap)) throw std::runtime_error("seg_attn_span: refused shape");
+  const int lpr = hd * (int)sizeof(Q) / 16;
+  hipLaunchKernelGGL((seg_attn_span_kernel<Q>), dim3(heads, n_items), dim3(256), (size_t)(maxS + 8) * 4, s,
+                     reinterpret_cast<const Q*>(q_keep), reinterpret_cast<const Q*>(kc), maxS, heads, hd, lpr, items,
+                     span_cap, scale, scratch);
+}
+template <typename Q>
+bool launch_seg_rephrase(const void* q_keep, const void* kc, int maxS, int heads, int hd, const float* hidden,
+                         const int* items, int n_items, int max_span, int span_cap, float* scratch, float scale,
+                         float weight, float* y, hipStream_t s) {
+  if (!seg_rephrase_shape_ok((int)sizeof(Q), hd, maxS, span_cap) || max_span > span_cap || heads < 1) return false;
+  if (((uintptr_t)q_keep | (uintptr_t)kc) & 15) return false;  // (16-byte loads; the rows are multiples of 16 bytes by the shape test)
+  if (n_items <= 0) return true;
+  launch_seg_attn_span<Q>(q_keep, kc, maxS, heads, hd, items, n_items, span_cap, scale, scratch, s);
+  launch_seg_rephrase_apply(hidden, maxS, heads * hd, heads, items, n_items, span_cap, scratch, weight, y, s);
+  return true;
+}
+template bool launch_seg_rephrase<float>(const void*, const void*, int, int, int, const float*, const int*, int, int, int,
+                                         float*, float, float, float*, hipStream_t);
+template bool launch_seg_rephrase<bf16>(const void*, const void*, int, int, int, const float*, const int*, int, int, int,
+                                        float*, float, float, float*, hipStream_t);
+template bool launch_seg_rephrase<f16>(const void*, const void*, int, int, int, const float*, const int*, int, int, int,
+                                       float*, float, float, float*, hipStream_t);
+template void launch_seg_attn_span<float>(const void*, const void*, int, int, int, const int*, int, int, float, float*,
+                                          hipStream_t);
+template void launch_seg_attn_span<bf16>(const void*, const void*, int, int, int, const int*, int, int, float, float*,
+                                         hipStream_t);
+template void launch_seg_attn_span<f16>(const void*, const void*, int, int, int, const int*, int, int, float, float*,
+                                        hipStream_t);
+
+// ---------------------------------------------------------------------------------------------
 // SAM decomposed relative-position bias tables (image_encoder.py:354-392; get_rel_pos with
 // q_size == k_size: R[q,k] = tab[q - k + size - 1]).
 // ---------------------------------------------------------------------------------------------

@@ -470,6 +470,23 @@ void launch_gather_rows(const float* x, int Smax, int D, const int* b, const int
 // y += w * sum_j p[j] * X[j,:]  with p normalised to sum 1 over [s,e)   (rephrase, anyref.py:746-755)
 void launch_rephrase(const float* hidden_b, int D, const float* attn_row, int s0, int e0, float weight,
                      float* y, hipStream_t s);
+// The rephrase branch of every image of a call in one launch pair (anyref_op_seg_rephrase states the arithmetic; DESIGN.md
+// §8.9).  items: device i32 [n_items][4] = (b, e0, s0, out_row); q_keep / kc Q [B, maxS, heads, hd]; hidden f32 [B, maxS, D],
+// y f32 [*, D], D = heads * hd; scratch f32 [n_items, heads, span_cap].  Pass A (attention.hip; grid heads x items) leaves
+// p_h[j], j in [s0, e0), in scratch; pass B (ops.hip; grid ceil(D / 256) x items) adds the weighted hidden rows to y.  No
+// atomics: bit-identical from run to run.  An item outside 0 <= s0 < e0 < maxS, e0 - s0 <= span_cap is skipped by both.
+// seg_rephrase_shape_ok: the shape test alone (elem_size = sizeof(Q)); the launcher also refuses max_span (largest e0 - s0,
+// known to the host) > span_cap and buffers that are not 16-byte aligned.  false: nothing was launched.
+bool seg_rephrase_shape_ok(int elem_size, int hd, int maxS, int span_cap);
+template <typename Q>
+void launch_seg_attn_span(const void* q_keep, const void* kc, int maxS, int heads, int hd, const int* items, int n_items,
+                          int span_cap, float scale, float* scratch, hipStream_t s);
+void launch_seg_rephrase_apply(const float* hidden, int maxS, int D, int heads, const int* items, int n_items, int span_cap,
+                               const float* scratch, float weight, float* y, hipStream_t s);
+template <typename Q>
+bool launch_seg_rephrase(const void* q_keep, const void* kc, int maxS, int heads, int hd, const float* hidden,
+                         const int* items, int n_items, int max_span, int span_cap, float* scratch, float scale,
+                         float weight, float* y, hipStream_t s);
 // convert generic dtype weight to f32 (dtype codes of anyref_hip.h)
 void launch_to_f32(const void* in, int dtype, float* out, int64_t n, hipStream_t s);
 

@@ -90,6 +90,11 @@ class ModelBase {
   void set_overlap(bool on) { overlap_ = on; }
   // masks of generated [SEG]s decoded on the side stream while the greedy loop goes on (default on; batch 1)
   void set_early_tail(bool on) { early_off_ = !on; }
+  // rephrase_weight > 0 on the fused launch pair, and with it under early masks, drafts and sessions (default off:
+  // anyref_set_rephrase_paths)
+  void set_rephrase_paths(bool on) { reph_paths_ = on; }
+  // masks the last generating call decoded early (anyref_early_masks_done)
+  int early_masks_done() const { return early_masks_last_; }
   // the NEXT generate / forward_teacher waits for this event on its stream just before it reads extra_embeds (the splice):
   // the caller may produce them (ImageBind audio trunk + projector) on a stream of its own, beside the CLIP tower
   void set_extra_event(void* ev) { extra_ev_ = ev; }
@@ -159,6 +164,8 @@ class ModelBase {
   int64_t inexact_ = 0;
   bool overlap_ = true;
   bool use_graphs_ = true;
+  bool reph_paths_ = false;   // set_rephrase_paths
+  int early_masks_last_ = 0;  // early_masks_done
   int side_wgs_ = getenv("ANYREF_SIDE_WGS") ? atoi(getenv("ANYREF_SIDE_WGS")) : 128;
   int side_steps_ = getenv("ANYREF_SIDE_STEPS") ? atoi(getenv("ANYREF_SIDE_STEPS")) : 6;
   int side_head_ = getenv("ANYREF_SIDE_HEAD") ? atoi(getenv("ANYREF_SIDE_HEAD")) : 3;  // encoder blocks queued beside CLIP

@@ -482,7 +482,7 @@ class Model : public ModelBase {
   // the verification pass of generate(): rows k[b] of the staged draft behind slen[b]; leaves the accept step's outputs in
   // drf_host_ (after ev_tok_[0]) and the decode-step state for whatever follows
   void draft_verify(hipStream_t s, int B, const std::vector<int>& slen, const std::vector<std::vector<int64_t>>& d,
-                    const std::vector<int>& k);
+                    const std::vector<int>& k, bool keep_q);
   // blocks [blk0, blk1) of the encoder; blk0 == 0 also runs the patch embedding, blk1 < 0 (= to the end) the neck
   void sam_encoder(hipStream_t s, const float* images, int B, float* out, int blk0 = 0, int blk1 = -1);
   void mask_decoder(hipStream_t s, const float* image_emb, const float* pred_emb, int n, float* masks4,
@@ -491,7 +491,7 @@ class Model : public ModelBase {
                 const std::vector<int>& seg_pos, const std::vector<int>& reph_s, const int32_t* resized_hw,
                 const int32_t* orig_hw, int32_t* out_nseg, float* out_masks, int64_t out_masks_cap,
                 int64_t* mask_offsets, float* out_low, const float* attn_given = nullptr, int attn_n = 0,
-                bool one_image = false);
+                bool one_image = false, bool pair = false);
   // generate() and session_generate() from "first token" to the end of the greedy loop: the lm_head pass on hidden row
   // slen[b] - 1 of every sequence, then the draft-verified or the plain one-token loop (hipGraph step, EOS / ahead rules).
   // `draft` is the call's (already taken) one-shot draft; fed / per_step: the encoder's CU share (generate only); early: early
@@ -499,6 +499,8 @@ class Model : public ModelBase {
   struct LoopArgs {
     int max_new_tokens = 0, eos_token_id = -1;
     bool keep_q = false, fed = false, early = false;
+    bool draft_keeps_q = false;  // the rephrase paths are on: a draft is verified under keep_q too (its pass keeps the queries)
+    int early_reph_s0 = -1;      // >= 0: the first early [SEG] also gets its rephrase term, over hidden rows [this, its row)
     int per_step = 0;
     const int32_t *resized_hw = nullptr, *orig_hw = nullptr;
     float* out_masks = nullptr;
@@ -512,7 +514,7 @@ class Model : public ModelBase {
   void join_sam(hipStream_t s);
   // mask of a [SEG] the greedy loop has just emitted, on the side stream, while the loop goes on (generate, batch 1)
   void early_seg(hipEvent_t hidden_ready, int hidden_row, const int32_t* resized_hw, const int32_t* orig_hw,
-                 float* out_masks, int64_t out_masks_cap, float* out_low);
+                 float* out_masks, int64_t out_masks_cap, float* out_low, int reph_s0);
   int early_done_ = 0;       // [SEG]s of this call already decoded by early_seg (in order of appearance)
   bool early_stop_ = false;  // a limit was hit: the tail decodes (or refuses) the rest
   // SAM image encoder on a second stream: it depends on nothing but the image, is MFMA-bound, and
@@ -539,6 +541,7 @@ class Model : public ModelBase {
     float* out_masks;
     int64_t cap;
     float* out_low;
+    int reph_s0;  // rephrase start row of the call (LoopArgs::early_reph_s0)
   };
   std::vector<PendingEarly> early_pending_;
   void early_seg_run(const PendingEarly& e);
@@ -554,6 +557,22 @@ class Model : public ModelBase {
                     const float* extra_embeds, const int32_t* extra_slots, int n_extra,
                     std::vector<int>& slen, std::vector<int>& img_pos);
   void ensure_q_last();
+  // The rephrase branch as one launch pair (anyref_set_rephrase_paths; launch_seg_rephrase).  The tail's item
+  // table and scratch belong to the caller's stream; the early path (side stream, while the decode loop owns kvlen_dev_,
+  // idx_a_ / idx_b_, attn_row_ and stage_kl_ on the caller's) has a table, a scratch and a staging region of its own.
+  int *reph_items_ = nullptr, *early_items_ = nullptr;      // dev i32 [max_batch][4] / [1][4]
+  float *reph_scratch_ = nullptr, *early_scratch_ = nullptr;  // dev f32 [max_batch, heads, S] / [heads, S]
+  void ensure_reph();
+  // the switch is on, the call rephrases and the pair takes this model: everything launch_seg_rephrase can refuse -- the
+  // shape, and query / key buffers that are not 16-byte aligned (max_span <= llm_max_seq = the scratch's span_cap always).
+  // Else: the per-image chain, as before
+  bool reph_pair() const {
+    const Q* kc = kcache_ + cache_layer_stride_ * (cfg.llm_layers - 1);
+    return reph_paths_ && cfg.rephrase_weight > 0.f && q_last_ && !(((uintptr_t)q_last_ | (uintptr_t)kc) & 15) &&
+           seg_rephrase_shape_ok((int)sizeof(Q), cfg.llm_dim / cfg.llm_heads, cfg.llm_max_seq, cfg.llm_max_seq);
+  }
+  // uploads `items` ((b, e0, s0, row of seg_h_) each) through staging region r and queues the pair on s
+  void reph_launch(hipStream_t s, int r, int* stage, const std::vector<int>& items, int* items_dev, float* scratch);
 
   // ---- CLIP ----
   struct ClipLayer {
@@ -602,9 +621,10 @@ class Model : public ModelBase {
   // NEXT call's indices.  The wait is free whenever the copy has already run (always, in generate's loop).
   int* stage_ = nullptr;
   int *stage_first_ = nullptr, *stage_extra_ = nullptr, *stage_seg_ = nullptr, *stage_kl_ = nullptr;
-  enum { ST_FIRST = 0, ST_EXTRA, ST_SEG, ST_KL, ST_N };
-  hipEvent_t stage_ev_[ST_N] = {nullptr, nullptr, nullptr, nullptr};
-  bool stage_busy_[ST_N] = {false, false, false, false};
+  int *stage_reph_ = nullptr, *stage_early_ = nullptr;  // item tables of the fused rephrase pair: the tail's, the early path's
+  enum { ST_FIRST = 0, ST_EXTRA, ST_SEG, ST_KL, ST_REPH, ST_EARLY, ST_N };
+  hipEvent_t stage_ev_[ST_N] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool stage_busy_[ST_N] = {false, false, false, false, false, false};
   void stage_begin(int r) {
     if (stage_busy_[r]) HIP_TRY(hipEventSynchronize(stage_ev_[r]));
     stage_busy_[r] = false;
@@ -964,11 +984,13 @@ void Model<T, TS>::finalize() {
     for (auto& e : ev_tok_) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     {
       const int n_first = 3 * MB, n_extra_max = 2 * MB * std::max(c.max_seg, 64), n_seg = 2 * MB * c.max_seg;
-      HIP_TRY(hipHostMalloc((void**)&stage_, sizeof(int) * (size_t)(n_first + n_extra_max + n_seg + MB)));
+      HIP_TRY(hipHostMalloc((void**)&stage_, sizeof(int) * (size_t)(n_first + n_extra_max + n_seg + MB + 4 * MB + 4)));
       stage_first_ = stage_;
       stage_extra_ = stage_first_ + n_first;
       stage_seg_ = stage_extra_ + n_extra_max;
       stage_kl_ = stage_seg_ + n_seg;
+      stage_reph_ = stage_kl_ + MB;
+      stage_early_ = stage_reph_ + 4 * MB;
       for (auto& e : stage_ev_) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     if (c.rephrase_weight > 0.f) ensure_q_last();
@@ -1344,6 +1366,32 @@ template <typename T, typename TS>
 void Model<T, TS>::ensure_q_last() {
   if (!q_last_) q_last_ = talloc<Q>((size_t)cfg.max_batch * cfg.llm_max_seq * cfg.llm_dim);
 }
+template <typename T, typename TS>
+void Model<T, TS>::ensure_reph() {
+  if (reph_items_) return;
+  const size_t MB = cfg.max_batch, per = (size_t)cfg.llm_heads * cfg.llm_max_seq;
+  reph_items_ = talloc<int>(4 * MB + 4);
+  early_items_ = reph_items_ + 4 * MB;
+  reph_scratch_ = talloc<float>((MB + 1) * per);
+  early_scratch_ = reph_scratch_ + MB * per;
+}
+template <typename T, typename TS>
+void Model<T, TS>::reph_launch(hipStream_t s, int r, int* stage, const std::vector<int>& items, int* items_dev, float* scratch) {
+  const anyref_config& c = cfg;
+  const int n = (int)items.size() / 4, S = c.llm_max_seq, nh = c.llm_heads, hd = c.llm_dim / nh;
+  if (n == 0) return;
+  int max_span = 0;
+  for (int i = 0; i < n; ++i) max_span = std::max(max_span, items[4 * i + 1] - items[4 * i + 2]);
+  {
+    StageScope stage_scope(this, r, s);
+    for (size_t i = 0; i < items.size(); ++i) stage[i] = items[i];
+    HIP_TRY(hipMemcpyAsync(items_dev, stage, items.size() * 4, hipMemcpyHostToDevice, s));
+  }
+  const Q* kc = kcache_ + cache_layer_stride_ * (c.llm_layers - 1);
+  if (!launch_seg_rephrase<Q>(q_last_, kc, S, nh, hd, hidden_all_, items_dev, n, max_span, S, scratch, 1.f / sqrtf((float)hd),
+                              c.rephrase_weight, seg_h_, s))
+    throw std::runtime_error("internal: the rephrase pair refused what reph_pair() had accepted");
+}
 
 // ---------------------------------------------------------------------------------------------
 // CLIP tower + projector
@@ -1673,7 +1721,7 @@ void Model<T, TS>::llm_extend(hipStream_t s, const float* embeds, const int32_t*
 
 template <typename T, typename TS>
 void Model<T, TS>::draft_verify(hipStream_t s, int B, const std::vector<int>& slen, const std::vector<std::vector<int64_t>>& d,
-                                const std::vector<int>& k) {
+                                const std::vector<int>& k, bool keep_q) {
   const anyref_config& c = cfg;
   const int H = c.llm_dim, S = c.llm_max_seq, V = c.llm_vocab;
   int n = 0;
@@ -1688,7 +1736,9 @@ void Model<T, TS>::draft_verify(hipStream_t s, int B, const std::vector<int>& sl
   ext_upload(s, slen.data(), k.data(), B, n, e);
   HIP_TRY(hipMemcpyAsync(drf_ids_, ids_h, (size_t)B * n * 8, hipMemcpyHostToDevice, s));
   launch_embed_rows(drf_ids_, B * n, emb_table_, kEmbDtype, H, l_x_, s);
-  llm_prefill(s, B, n, e.lens, false, &e);
+  // keep_q: the last layer's rotated queries of the pass's rows go to q_last_ at slen[b] + i, as a decode step leaves them (a
+  // rejected row's query is overwritten by the step that redoes its position, like its K and V)
+  llm_prefill(s, B, n, e.lens, keep_q, &e);
   for (int b = 0; b < B; ++b)
     if (k[b] > 0)
       launch_convert<T>(hidden_all_ + ((size_t)b * S + slen[b]) * H, H, l_h_ + (size_t)b * n * apad<T>(H), apad<T>(H), k[b], H, s);
@@ -2032,8 +2082,8 @@ struct SamJoinGuard {
 // the loop (the reference always emits at least the EOS after a [SEG]; ~1 ms per image at batch 1).
 template <typename T, typename TS>
 void Model<T, TS>::early_seg(hipEvent_t hidden_ready, int hidden_row, const int32_t* resized_hw, const int32_t* orig_hw,
-                         float* out_masks, int64_t out_masks_cap, float* out_low) {
-  const PendingEarly e{hidden_ready, hidden_row, resized_hw, orig_hw, out_masks, out_masks_cap, out_low};
+                         float* out_masks, int64_t out_masks_cap, float* out_low, int reph_s0) {
+  const PendingEarly e{hidden_ready, hidden_row, resized_hw, orig_hw, out_masks, out_masks_cap, out_low, reph_s0};
   if (!sam_enq_done_) {  // blocks still to be fed: the mask is queued behind the last of them (sam_feed)
     if ((int)early_pending_.size() + early_done_ >= cfg.max_seg) early_stop_ = true;
     else early_pending_.push_back(e);
@@ -2053,6 +2103,11 @@ void Model<T, TS>::early_seg_run(const PendingEarly& e) {
   HIP_TRY(hipStreamWaitEvent(s2_, e.ready, 0));
   HIP_TRY(hipMemcpyAsync(seg_h_ + (size_t)slot * H, hidden_all_ + (size_t)e.hidden_row * H, (size_t)H * 4,
                          hipMemcpyDeviceToDevice, s2_));
+  // Rephrasing (anyref.py:735-755): the first [SEG] of the row gets + w * sum_j a_j * hidden_j over rows [s0, e0).  Row e0's query,
+  // keys [0, e0] and those hidden rows are final behind `ready`; the loop on the caller's stream only ever writes rows > e0.  Item
+  // table, staging and scratch are this path's own: kvlen_dev_, idx_a_ / idx_b_, attn_row_ and stage_kl_ belong to that loop.
+  if (slot == 0 && e.reph_s0 >= 0 && e.hidden_row > e.reph_s0)
+    reph_launch(s2_, ST_EARLY, stage_early_, {0, e.hidden_row, e.reph_s0, 0}, early_items_, early_scratch_);
   gemmf(s2_, seg_h_ + (size_t)slot * H, H, fc1_, seg_t_ + (size_t)slot * H, H, 1, ACT_RELU);
   gemmf(s2_, seg_t_ + (size_t)slot * H, H, fc2_, pred_emb_ + (size_t)slot * c.out_dim, c.out_dim, 1, ACT_NONE);
   mask_decoder(s2_, sam_emb_, pred_emb_ + (size_t)slot * c.out_dim, 1, nullptr, nullptr);
@@ -2068,10 +2123,12 @@ template <typename T, typename TS>
 void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const std::vector<int>& seg_b,
                         const std::vector<int>& seg_pos, const std::vector<int>& reph_s, const int32_t* resized_hw,
                         const int32_t* orig_hw, int32_t* out_nseg, float* out_masks, int64_t out_masks_cap,
-                        int64_t* mask_offsets, float* out_low, const float* attn_given, int attn_n, bool one_image) {
+                        int64_t* mask_offsets, float* out_low, const float* attn_given, int attn_n, bool one_image,
+                        bool pair) {
   // seg_b/seg_pos: (image, row of hidden_all_) of every [SEG]; reph_s: rephrase start row per image
   // attn_given (seg_tail only): caller's head-mean last-layer attention [B, attn_n, attn_n] instead of the K cache
   // one_image (session_generate only): every row is about the image whose embedding sits in slot 0 of sam_emb_ already
+  // pair (generate / session_generate with reph_pair()): the rephrase terms by the fused launch pair, not the per-image chain
   const anyref_config& c = cfg;
   const int H = c.llm_dim, S = c.llm_max_seq, nseg = (int)seg_b.size();
   // join BEFORE anything below can throw: a refused call must not leave the encoder running on the side stream
@@ -2080,6 +2137,7 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
   const bool sam_ready = sam_forked_;
   const int done = early_done_;  // generate, batch 1: rows [0, done) were decoded by early_seg, masks and all
   early_done_ = 0;
+  early_masks_last_ = done;
   join_sam(s);
   for (int b = 0; b < B; ++b) out_nseg[b] = 0;
   for (int i = 0; i < nseg; ++i) out_nseg[seg_b[i]]++;
@@ -2103,7 +2161,21 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
     HIP_TRY(hipMemcpyAsync(idx_b_, stage_seg_ + nseg, nseg * 4, hipMemcpyHostToDevice, s));
   }
   launch_gather_rows(hidden_all_, S, H, idx_a_, idx_b_, nseg, seg_h_, s);
-  if (c.rephrase_weight > 0.f) {
+  if (c.rephrase_weight > 0.f && pair) {
+    // every image's term behind one item table, one launch pair (launch_seg_rephrase); a [SEG] the early path has
+    // decoded (rows [0, early) of a one-image generate) had its term there
+    std::vector<int> items;
+    std::vector<char> seen(B, 0);
+    for (int i = 0; i < nseg; ++i) {
+      const int b = seg_b[i];
+      if (seen[b]) continue;
+      seen[b] = 1;
+      const int e0 = seg_pos[i], s0 = reph_s[b];
+      if (e0 <= s0 || i < done) continue;
+      items.insert(items.end(), {b, e0, s0, i});
+    }
+    reph_launch(s, ST_REPH, stage_reph_, items, reph_items_, reph_scratch_);
+  } else if (c.rephrase_weight > 0.f) {
     StageScope stage_scope(this, ST_KL, s);  // (the event is recorded at the end of this block whether or not a copy was queued)
     // anyref.py:735-755,767-769: the first [SEG] of image i gets + w * sum_j attn_j * hidden_j
     const int nh = c.llm_heads, hd = H / nh;
@@ -2174,6 +2246,9 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
   if (!draft.empty() && (int)draft.size() != B) throw std::runtime_error("the pending draft was set for another batch size");
   const int H = c.llm_dim, S = c.llm_max_seq, n_img = clip_n_;
   const bool keep_q = c.rephrase_weight > 0.f;
+  const bool pair = reph_pair();
+  early_masks_last_ = 0;
+  if (pair) ensure_reph();
 
   SamJoinGuard<Model<T, TS>> join_guard{this, s};
   // Batch 1 with a CU share set: the encoder is fed to the side stream a few capped blocks at a time (fork_sam's
@@ -2229,15 +2304,18 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
   } else {
     fork_sam(s, sam_images, B);
   }
-  // early [SEG] masks: batch 1, encoder on the side stream, no rephrasing (that reads attention over the whole answer),
-  // no [SEG] inside the prompt (the tail's order is by position)
+  // early [SEG] masks: batch 1, encoder on the side stream, no [SEG] inside the prompt (the tail's order is by position), and no
+  // rephrasing unless the fused pair serves it (the per-image chain works in buffers the decode loop owns; the pair reads the
+  // answer up to the [SEG] only, all final when the token is read: DESIGN.md §8.9)
   early_done_ = 0;
   early_stop_ = false;
-  bool early = !early_off_ && sam_forked_ && B == 1 && c.rephrase_weight <= 0.f;
+  bool early = !early_off_ && sam_forked_ && B == 1 && (c.rephrase_weight <= 0.f || pair);
   for (int i = 1; early && i < lens[0]; ++i)
     if (input_ids[i] >= c.seg_lo && input_ids[i] <= c.seg_hi) early = false;
   LoopArgs la;
   la.max_new_tokens = max_new_tokens; la.eos_token_id = eos_token_id; la.keep_q = keep_q; la.fed = fed; la.early = early;
+  la.draft_keeps_q = reph_paths_;
+  if (early && pair) la.early_reph_s0 = lens[0] - 1 + (img_pos[0] >= 0 ? n_img - 1 : 0);  // reph[0] below
   la.per_step = per_step; la.resized_hw = resized_hw; la.orig_hw = orig_hw; la.out_masks = out_masks;
   la.out_masks_cap = out_masks_cap; la.out_low = out_low;
   std::vector<std::vector<int64_t>> gen;
@@ -2265,7 +2343,7 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
     reph[b] = lens[b] - 1 + shift;  // input_ids[i,1:].shape[0] + 255 (anyref.py:745)
   }
   run_tail(s, sam_images, B, seg_b, seg_pos, reph, resized_hw, orig_hw, out_nseg, out_masks, out_masks_cap,
-           mask_offsets, out_low);
+           mask_offsets, out_low, nullptr, 0, false, pair);
   if (out_hidden)
     HIP_TRY(hipMemcpyAsync(out_hidden, hidden_all_, (size_t)B * S * H * 4, hipMemcpyDeviceToDevice, s));
 }
@@ -2325,7 +2403,9 @@ void Model<T, TS>::decode_loop(hipStream_t s, int B, const std::vector<int>& sle
   // left the plain loop below runs, launch for launch as without a draft.
   std::vector<int> dk(B, 0);
   bool drafted = false;
-  if (!draft.empty() && !keep_q) {  // rephrasing reads the attention of the whole answer: the draft is ignored (offered = 0)
+  // rephrasing off the fused paths: the draft is ignored (offered = 0), as ever.  On them: the term reads the
+  // query of the row that predicted the [SEG], and the verification pass keeps its rows' queries like a step
+  if (!draft.empty() && (!keep_q || la.draft_keeps_q)) {
     for (int b = 0; b < B; ++b) {
       int k = 0;
       while (k < (int)draft[b].size() && draft[b][k] >= 0 && draft[b][k] < c.llm_vocab) ++k;
@@ -2345,7 +2425,7 @@ void Model<T, TS>::decode_loop(hipStream_t s, int B, const std::vector<int>& sle
       if (eos_token_id >= 0 && t == eos_token_id) fin[b] = 1;
       if (g + 1 >= max_new_tokens) fin[b] = 1;
       if (early && !early_stop_ && t >= c.seg_lo && t <= c.seg_hi)
-        early_seg(ready, slen[0] + g - 1, resized_hw, orig_hw, out_masks, out_masks_cap, out_low);
+        early_seg(ready, slen[0] + g - 1, resized_hw, orig_hw, out_masks, out_masks_cap, out_low, la.early_reph_s0);
     };
     // the first token decides whether a row's draft is worth a pass at all
     int64_t* t0 = next_host_;
@@ -2360,7 +2440,7 @@ void Model<T, TS>::decode_loop(hipStream_t s, int B, const std::vector<int>& sle
     if (any) {
       int n = 0;
       for (int b = 0; b < B; ++b) n = std::max(n, dk[b]);
-      draft_verify(s, B, slen, draft, dk);  // waits for the accept step's results
+      draft_verify(s, B, slen, draft, dk, keep_q);  // waits for the accept step's results
       stat_passes_ = 1;
       const int64_t* tok_h = drf_host_ + (size_t)c.max_batch * kDraftCap;
       const int* acc_h = reinterpret_cast<const int*>(tok_h + (size_t)c.max_batch * (kDraftCap + 1));
@@ -2406,7 +2486,8 @@ void Model<T, TS>::decode_loop(hipStream_t s, int B, const std::vector<int>& sle
         if (eos_token_id >= 0 && tok[b] == eos_token_id) fin[b] = 1;
         // token `step` was predicted by hidden row slen + step - 1, final since ev_tok_ of this step
         if (early && !early_stop_ && tok[b] >= c.seg_lo && tok[b] <= c.seg_hi)
-          early_seg(ev_tok_[step & 1], slen[0] + step - 1, resized_hw, orig_hw, out_masks, out_masks_cap, out_low);
+          early_seg(ev_tok_[step & 1], slen[0] + step - 1, resized_hw, orig_hw, out_masks, out_masks_cap, out_low,
+                    la.early_reph_s0);
       }
       all = all && fin[b];
     }
@@ -2479,7 +2560,7 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
   }
   if (nq < 1 || nq > c.max_batch) throw std::runtime_error("session_generate: queries outside [1, max_batch]");
   if (max_new_tokens < 1) throw std::runtime_error("max_new_tokens must be >= 1");
-  if (c.rephrase_weight > 0.f)
+  if (c.rephrase_weight > 0.f && !reph_paths_)  // (served with anyref_set_rephrase_paths on: DESIGN.md §8.9)
     throw std::runtime_error("session_generate: rephrase_weight > 0 is not served inside a session (rephrasing reads the last "
                              "layer's queries of the whole prompt, which the extend path does not keep)");
   if (!suffix_ids || !lens || !out_ids || !out_lens || !out_nseg || !mask_offsets) throw std::runtime_error("session_generate: null argument");
@@ -2511,6 +2592,11 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
   for (int b = 0; b < nq; ++b) slen[b] = P + lens[b];
   early_done_ = 0;  // see forward_teacher
   early_stop_ = false;
+  early_masks_last_ = 0;
+  const bool keep_q = c.rephrase_weight > 0.f;
+  if (keep_q) ensure_q_last();
+  const bool pair = reph_pair();
+  if (pair) ensure_reph();
   // ---- 1. the prefix for cache rows that do not hold it yet: K, V of every layer in one launch, the hidden rows in another ----
   if (nq > sess_rows_) {
     constexpr int64_t kv_elem = sizeof(Q);  // the cache element (the class's type Q: f32 in the parity modes, 16-bit in perf)
@@ -2545,10 +2631,13 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
   // ---- 3, 4. the extend pass: n rows per query behind the prefix ----
   PrefillExt e;
   ext_upload(s, pos0.data(), lens, nq, n, e);
+  // No q_keep for the suffix rows, rephrasing or not: the term reads the query of row e0 only, the row that predicted the [SEG],
+  // and run_tail skips e0 <= s0 = slen[b] - 1 -- every query it reads lies behind the prompt, written by a decode step or by a
+  // draft's verification pass.
   llm_prefill(s, nq, n, e.lens, false, &e);
   // ---- 5, 6. first token and the greedy loop ----
   LoopArgs la;
-  la.max_new_tokens = max_new_tokens; la.eos_token_id = eos_token_id;
+  la.max_new_tokens = max_new_tokens; la.eos_token_id = eos_token_id; la.keep_q = keep_q; la.draft_keeps_q = reph_paths_;
   std::vector<std::vector<int64_t>> gen;
   decode_loop(s, nq, slen, draft, la, gen);
   // ---- 7. ids and masks: generate()'s arithmetic on prefix + suffix + answer, every row about the one image ----
@@ -2570,6 +2659,7 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
         seg_pos.push_back(hp);
       }
     }
+    reph[b] = slen[b] - 1;  // generate()'s lens[b] - 1 + shift on prefix + suffix (read with rephrase_weight > 0 only)
   }
   sess_hw_.resize((size_t)4 * nq);
   for (int b = 0; b < nq; ++b)
@@ -2578,7 +2668,7 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
       sess_hw_[2 * nq + 2 * b + i] = sess_ohw_[i];
     }
   run_tail(s, nullptr, nq, seg_b, seg_pos, reph, sess_hw_.data(), sess_hw_.data() + 2 * nq, out_nseg, out_masks, out_masks_cap,
-           mask_offsets, out_low, nullptr, 0, true);
+           mask_offsets, out_low, nullptr, 0, true, pair);
   if (out_hidden)
     HIP_TRY(hipMemcpyAsync(out_hidden, hidden_all_, (size_t)nq * S * H * 4, hipMemcpyDeviceToDevice, s));
 }

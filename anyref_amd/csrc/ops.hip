@@ -1397,6 +1397,58 @@ void launch_rephrase(const float* hidden_b, int D, const float* attn_row, int s0
                      y);
 }
 
+// Rephrase branch, pass B (launch_seg_rephrase in kernels.h): w_j = mean over heads of pass A's p_h[j] (heads in order), tot =
+// sum_j w_j (lane-strided, then the xor butterfly: a fixed order), y[out_row, d] += weight * sum_j hidden[b, j, d] * (w_j / tot).
+// Every workgroup of an item recomputes the <= span_cap weights: they are heads * span floats out of L2.
+__global__ __launch_bounds__(256) void seg_rephrase_apply_kernel(const float* __restrict__ hidden, int maxS, int D, int heads,
+                                                                 const int* __restrict__ items, int span_cap,
+                                                                 const float* __restrict__ scratch, float weight,
+                                                                 float* __restrict__ y) {
+  extern __shared__ float seg_w[];  // [span_cap] w_j, then w_j / tot; [1] tot
+  const int it = blockIdx.y, tid = threadIdx.x;
+  const int b = items[4 * it], e0 = items[4 * it + 1], s0 = items[4 * it + 2], out_row = items[4 * it + 3];
+  if (s0 < 0 || e0 <= s0 || e0 >= maxS || e0 - s0 > span_cap) return;  // (the same for every thread)
+  const int span = e0 - s0;
+  const float* p = scratch + (int64_t)it * heads * span_cap;
+  const float inv = 1.f / (float)heads;
+  for (int j = tid; j < span; j += 256) {
+    float a = 0.f;
+    for (int h = 0; h < heads; ++h) a += p[(int64_t)h * span_cap + j];
+    seg_w[j] = inv * a;
+  }
+  __syncthreads();
+  if (tid < 64) {
+    float t = 0.f;
+    for (int j = tid; j < span; j += 64) t += seg_w[j];
+    t = wave_sum(t);
+    if (tid == 0) seg_w[span_cap] = t;
+  }
+  __syncthreads();
+  const float tot = seg_w[span_cap];
+  for (int j = tid; j < span; j += 256) seg_w[j] = seg_w[j] / tot;
+  __syncthreads();
+  const int d = blockIdx.x * 256 + tid;
+  if (d >= D) return;
+  const float* hb = hidden + ((int64_t)b * maxS + s0) * D + d;
+  float acc = 0.f;
+  for (int j = 0; j < span; ++j) acc = fmaf(hb[(int64_t)j * D], seg_w[j], acc);
+  y[(int64_t)out_row * D + d] += weight * acc;
+}
+bool seg_rephrase_shape_ok(int elem_size, int hd, int maxS, int span_cap) {
+  if (hd < 1 || maxS < 2 || span_cap < 1 || (elem_size != 2 && elem_size != 4)) return false;
+  const int bytes = hd * elem_size, lpr = bytes / 16;
+  if (bytes % 16 || lpr > 64 || (lpr & (lpr - 1))) return false;  // the lanes of a key row: a power of two inside one wave
+  if (((int64_t)maxS + 8) * 4 > 65536 || ((int64_t)span_cap + 1) * 4 > 65536) return false;  // score row / weights in LDS
+  return true;
+}
+void launch_seg_rephrase_apply(const float* hidden, int maxS, int D, int heads, const int* items, int n_items, int span_cap,
+                               const float* scratch, float weight, float* y, hipStream_t s) {
+  if (n_items <= 0) return;
+  if (((int64_t)span_cap + 1) * 4 > 65536) throw std::runtime_error("seg_rephrase_apply: span_cap past the LDS");
+  hipLaunchKernelGGL(seg_rephrase_apply_kernel, dim3(cdiv(D, 256), n_items), dim3(256), (size_t)(span_cap + 1) * 4, s, hidden,
+                     maxS, D, heads, items, span_cap, scratch, weight, y);
+}
+
 __global__ void to_f32_kernel(const void* __restrict__ in, int dtype, float* __restrict__ out, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float v;

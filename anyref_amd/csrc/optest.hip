@@ -298,6 +298,44 @@ int anyref_op_decode_attn(int t, void* stream, const float* qkv, int B, int H, i
   });
 }
 
+int anyref_op_seg_rephrase(int t, void* stream, const void* q_keep, const void* kc, int maxS, int H, int hd, const float* hidden,
+                           const int32_t* items, int n_items, int max_span, int span_cap, float* scratch, float scale,
+                           float weight, float* y, int32_t* launched) {
+  OP_GUARD({
+    if (t != 0 && t != 1 && t != 2) throw std::runtime_error("op_seg_rephrase: t = 0 / 1 / 2");
+    if (!q_keep || !kc || !hidden || !items || !scratch || !y || !launched) throw std::runtime_error("op_seg_rephrase: null argument");
+    if (n_items < 0 || maxS < 1 || H < 1 || hd < 1) throw std::runtime_error("op_seg_rephrase: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    bool ok;
+    if (t == 0)
+      ok = launch_seg_rephrase<float>(q_keep, kc, maxS, H, hd, hidden, items, n_items, max_span, span_cap, scratch, scale, weight, y, st);
+    else if (t == 2)
+      ok = launch_seg_rephrase<f16>(q_keep, kc, maxS, H, hd, hidden, items, n_items, max_span, span_cap, scratch, scale, weight, y, st);
+    else
+      ok = launch_seg_rephrase<bf16>(q_keep, kc, maxS, H, hd, hidden, items, n_items, max_span, span_cap, scratch, scale, weight, y, st);
+    *launched = ok ? 1 : 0;
+  });
+}
+
+int anyref_op_rephrase_chain(int t, void* stream, const void* q_keep, const void* kc, int maxS, int H, int hd,
+                             const float* hidden, int b, int e0, int s0, const int32_t* kv_len, float* attn_row, float scale,
+                             float weight, float* y) {
+  OP_GUARD({
+    if (t != 0 && t != 1 && t != 2) throw std::runtime_error("op_rephrase_chain: t = 0 / 1 / 2");
+    if (!q_keep || !kc || !hidden || !kv_len || !attn_row || !y) throw std::runtime_error("op_rephrase_chain: null argument");
+    if (b < 0 || s0 < 0 || e0 <= s0 || e0 >= maxS) throw std::runtime_error("op_rephrase_chain: bad item");
+    hipStream_t st = (hipStream_t)stream;
+    const int D = H * hd;
+    const size_t es = t == 0 ? 4 : 2;
+    const char* q = (const char*)q_keep + ((size_t)b * maxS + e0) * D * es;
+    const char* k = (const char*)kc + (size_t)b * maxS * D * es;
+    if (t == 0) launch_attn_row_mean<float>(q, 0, hd, k, 0, D, hd, kv_len, 1, H, hd, scale, attn_row, maxS, st);
+    else if (t == 2) launch_attn_row_mean<f16>(q, 0, hd, k, 0, D, hd, kv_len, 1, H, hd, scale, attn_row, maxS, st);
+    else launch_attn_row_mean<bf16>(q, 0, hd, k, 0, D, hd, kv_len, 1, H, hd, scale, attn_row, maxS, st);
+    launch_rephrase(hidden + (size_t)b * maxS * D, D, attn_row, s0, e0, weight, y, st);
+  });
+}
+
 int anyref_op_rope_cache(int t, void* stream, const void* qkv, const float* slab0, const float* slab1, int B, int S, int H,
                          int hd, const int32_t* pos0, const int32_t* lens, const float* cs_tab, void* q_out, void* kc,
                          void* vc, int maxS, void* q_keep) {

@@ -68,7 +68,8 @@ def _c_config(cfg: AnyRefConfig, mode: int, max_batch: int, max_seg: int) -> _li
 _NEEDS_HANDLE = frozenset({
     "generate", "model_forward_new", "forward", "__call__", "encode_images", "sam_encode", "mask_decode", "llm_forward",
     "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
-    "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session"})
+    "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session",
+    "set_rephrase_paths", "early_masks_done"})
 
 
 class AnyRefForCausalLM:
@@ -357,6 +358,17 @@ class AnyRefForCausalLM:
     def set_early_tail(self, on: bool):
         """Masks of generated [SEG]s decoded on the side stream while the greedy loop goes on (default; batch 1)."""
         self._check(self.lib.anyref_set_early_tail(self.h, int(on)), "set_early_tail")
+
+    @property
+    def early_masks_done(self) -> int:
+        """masks the last `generate` / session `generate` decoded early, on the side stream (0: the path did not run)"""
+        return int(self.lib.anyref_early_masks_done(self.h))
+
+    def set_rephrase_paths(self, on: bool):
+        """`rephrase_weight > 0` on the fast paths (default off): the rephrase term of every image by one fused
+        launch pair, and with it early [SEG] masks, drafts and image sessions under rephrasing.  Off: rephrasing runs its
+        per-image chain after the loop, ignores drafts and is refused inside a session, as before the switch existed."""
+        self._check(self.lib.anyref_set_rephrase_paths(self.h, int(on)), "set_rephrase_paths")
 
     def set_graphs(self, on: bool):
         """hipGraph replay of the greedy decode step (default) or eager launches."""
@@ -756,8 +768,11 @@ class AnyRefForCausalLM:
             return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **self.draft_stats(B))
         return res
 
-    def _result(self, out_ids, out_lens, out_nseg, offs, out_masks, height, width):
-        """what `generate` returns, from the buffers anyref_generate / anyref_session_generate filled"""
+    def _result(self, out_ids, out_lens, out_nseg, offs, out_masks, height, width, per_row=False):
+        """what `generate` returns, from the buffers anyref_generate / anyref_session_generate filled.  per_row (a session: its
+        rows are independent queries, each what a one-row plain call returns): the reference's "fewer [SEG]s than samples"
+        rule under rephrasing is a property of ONE batched call and is not applied across the rows -- a row without a [SEG]
+        gets an empty [0, h, w] mask tensor, the other rows keep their masks"""
         B = out_ids.shape[0]
         # HF pads finished rows with pad_token_id
         full = torch.full((B, int(out_lens.max())), int(self.config.pad_token_id or 0), dtype=torch.long)
@@ -767,7 +782,7 @@ class AnyRefForCausalLM:
         total = int(out_nseg.sum())
         if total == 0:                                    # anyref.py:729-730
             res = (output_ids, None, (None, None, None))
-        elif self.cfg.rephrase_weight > 0 and total < B:  # (3-tuple in the reference too)
+        elif self.cfg.rephrase_weight > 0 and total < B and not per_row:  # (3-tuple in the reference too)
             # anyref.py:739-744,763-765: with rephrase on, the reference indexes the flattened [SEG] list by sample; fewer
             # [SEG] tokens than samples is its IndexError -> `no_mask` path: one all-zero [1, height[0], width[0]] mask per
             # sample (the same tensor object bs times), whatever the other rows produced
@@ -780,7 +795,7 @@ class AnyRefForCausalLM:
                 o = int(offs[b])
                 pred_masks.append(out_masks[o: o + n * h * w].view(n, h, w))
             res = (output_ids, pred_masks, (None, None, None))
-        if self.success_arity == 2 and res[1] is not None and not (self.cfg.rephrase_weight > 0 and total < B):
+        if self.success_arity == 2 and res[1] is not None and not (self.cfg.rephrase_weight > 0 and total < B and not per_row):
             res = res[:2]                                 # the reference's own success path (anyref.py:822): any [SEG], no `no_mask`
         return res
 
@@ -970,7 +985,7 @@ class ImageSession:
             m.h, m._stream(), _ptr(suf), _ptr(slens), Q, Lmax, _ptr(extra), _ptr(slots), n_extra, int(max_new_tokens), int(eos),
             _ptr(out_ids), _ptr(out_lens), _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)),
             "session_generate")
-        res = m._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width)
+        res = m._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width, per_row=True)
         if _return_extras:
             return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **m.draft_stats(Q))
         return res

@@ -237,11 +237,24 @@ int anyref_set_seg_range(anyref_handle* h, int lo, int hi);
  * call on the caller's stream (used by bench.py to time kernels without a co-running stream). */
 int anyref_set_overlap(anyref_handle* h, int on);
 
-/* Early [SEG] masks (default 1; effective with overlap on, batch 1, rephrase_weight 0, no [SEG] in the prompt):
+/* Early [SEG] masks (default 1; effective with overlap on, batch 1, no [SEG] in the prompt, and rephrase_weight 0 or
+ * anyref_set_rephrase_paths on):
  * anyref_generate queues the hand-off MLP, mask decoder and postprocess of a generated [SEG] on the side stream the
  * moment the token is read, under the remaining decode steps (the reference runs them after generate() returns,
- * anyref.py:718-822; same arithmetic per prompt, one prompt per mask-decoder call).  0: all masks after the loop. */
+ * anyref.py:718-822; same arithmetic per prompt, one prompt per mask-decoder call).  0: all masks after the loop.
+ * Under rephrasing the first [SEG]'s rephrase term is queued there too, in front of the MLP: it reads the [SEG] row's
+ * query, keys [0, e0] and hidden rows [s0, e0), all final when the token is read. */
 int anyref_set_early_tail(anyref_handle* h, int on);
+/* masks the last anyref_generate / anyref_session_generate decoded early (0 when the path did not run) */
+int anyref_early_masks_done(anyref_handle* h);
+
+/* The rephrase branch (rephrase_weight > 0) on the fast paths (default 0).  1: the rephrase term of every
+ * image is computed by one launch pair behind a device table of (image, [SEG] row, start row, output row) items
+ * (anyref_op_seg_rephrase) instead of one small launch chain per image; early [SEG] masks, anyref_set_draft and
+ * anyref_session_generate then serve rephrase_weight > 0 as they serve 0.  Where the pair refuses a shape the per-image
+ * chain runs, and early masks stay off under rephrasing.  0: every entry queues what it queued before this switch
+ * existed.  No effect with rephrase_weight 0, on anyref_forward_teacher or on anyref_seg_tail. */
+int anyref_set_rephrase_paths(anyref_handle* h, int on);
 
 /* extra_embeds produced on ANOTHER stream (e.g. the ImageBind audio trunk + audio_projector, `anyref_audio_encode` /
  * `anyref_project_audio` on a stream of the caller's): the next anyref_generate / anyref_forward_teacher on this handle makes
@@ -263,7 +276,9 @@ int anyref_set_extra_event(anyref_handle* h, void* event);
  * lm_head on those rows and the accept step (anyref_op_draft_accept): with g[0] = t0, g[j + 1] = argmax(logits[j]), the
  * accepted count m_b is the number of leading j < k_b with g[j] == d[j], and g[0 .. m_b] are appended to the row (EOS and
  * max_new_tokens applied per row).  The one-token loop then continues, graph replay included, until every row has ended.
- * At most one verification pass per call.  With rephrase_weight > 0 the draft is ignored (offered = 0). */
+ * At most one verification pass per call.  With rephrase_weight > 0 the draft is ignored (offered = 0) unless
+ * anyref_set_rephrase_paths is on: then the pass keeps the last layer's rotated queries of its rows as a decode step does
+ * (rejected rows' queries are overwritten by the steps that follow, like their K and V). */
 int anyref_set_draft(anyref_handle* h, const int64_t* draft_ids, const int32_t* draft_lens, int B, int Kmax);
 /* After anyref_generate: per row, the draft tokens fed to the verification pass and how many were accepted;
  * decode steps launched by the call; verification passes (0 or 1).  Any pointer may be NULL. */
@@ -302,8 +317,9 @@ int anyref_session_open(anyref_handle* h, void* stream, const float* clip_image,
  * CU share and early masks do not apply.  A pending anyref_set_draft is honoured under the rules stated there with
  * slen[b] = P + lens[b], one-shot and consumed by this call whatever happens; anyref_draft_stats reports the call's counters.
  * Refused before anything is queued, the session staying usable: P + lens[b] + max_new_tokens > llm_max_seq, lens[b] < 1, Q
- * outside [1, max_batch], an image placeholder inside a suffix, and rephrase_weight > 0 (rephrasing reads the last layer's
- * queries of the whole prompt, which the extend path does not keep -- as a draft is ignored under rephrasing).
+ * outside [1, max_batch], an image placeholder inside a suffix, and rephrase_weight > 0 while anyref_set_rephrase_paths is
+ * off.  With it on, rephrasing is served: the term reads the query of the row that predicted the [SEG], which lies behind the
+ * prompt (e0 > s0 = P + lens[b] - 1) and so comes from a decode step or a draft's pass, never from the suffix pass.
  * Any other entry that writes row 0 of the KV cache or of the hidden states, the CLIP feature buffer or image-embedding slot 0
  * ends the session: anyref_generate, anyref_forward_teacher, anyref_llm_forward, anyref_llm_extend, anyref_seg_tail,
  * anyref_encode_images, anyref_finalize.  The next anyref_session_generate then fails with "session lost: ended by <entry>".

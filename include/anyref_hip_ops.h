@@ -39,6 +39,22 @@ int anyref_op_rope_table(int S, int hd, float theta, float* out_host);
 int anyref_op_decode_attn(int t, void* stream, const float* qkv, int B, int H, int hd, const int32_t* pos,
                           const float* cs_tab, void* kc, void* vc, int maxS, float scale, float* out, void* q_keep,
                           int force_fallback);
+/* the rephrase branch as one launch pair (t = 0 f32 / 1 bf16 / 2 f16 cache).  items i32 dev [n_items][4] =
+ * (b, e0, s0, out_row) with 0 <= s0 < e0 < maxS; q_keep / kc T [B, maxS, H, hd] (rotated queries, keys of the last layer),
+ * hidden f32 [B, maxS, H*hd].  Per item: p_h = softmax_j(scale * q[b, e0, h] . k[b, j, h]) over keys j in [0, e0]; w_j = mean_h
+ * p_h[j] for j in [s0, e0); y[out_row, :] += weight * sum_j hidden[b, j, :] * (w_j / sum_j w_j).  scratch f32 [n_items, H,
+ * span_cap]; max_span = the largest e0 - s0 of the items (the host knows it).  *launched = 1, or 0 where the launcher refuses by
+ * shape (hd * sizeof(T) no multiple of 16 or more than 64 such pieces / not a power of two of them, the score row of maxS
+ * floats or span_cap floats past 64 KB of LDS, max_span > span_cap, a buffer not 16-byte aligned): then nothing was written */
+int anyref_op_seg_rephrase(int t, void* stream, const void* q_keep, const void* kc, int maxS, int H, int hd, const float* hidden,
+                           const int32_t* items, int n_items, int max_span, int span_cap, float* scratch, float scale,
+                           float weight, float* y, int32_t* launched);
+/* the same term for ONE item by the per-image chain (the head-mean attention row of query e0 over kv_len[0] = e0 + 1 keys into
+ * attn_row f32 [maxS], then y f32 [H*hd] += weight * sum_j hidden[b, j] * attn_row[j] / sum): what runs with
+ * anyref_set_rephrase_paths off, here for timing one against the other (tools/ab_session.py) */
+int anyref_op_rephrase_chain(int t, void* stream, const void* q_keep, const void* kc, int maxS, int H, int hd,
+                             const float* hidden, int b, int e0, int s0, const int32_t* kv_len, float* attn_row, float scale,
+                             float weight, float* y);
 /* prefill RoPE + KV append (t = 0 f32 / 1 bf16 / 2 f16): qkv T [B, S, 3, H, hd], or (slab0 non-NULL) the sum of two f32 slabs
  * of that shape (rounded to T first; t = 0: not rounded); rows s < lens[b] (all if lens is NULL) go to position pos0[b] + s (pos0 NULL: 0); q_out T [B, S, H, hd],
  * kc / vc / q_keep T [B, maxS, H, hd] */

@@ -13,10 +13,14 @@ per case), so that clock and neighbour drift fall on all alike:
 Before the timing, untimed, every case's output is checked against the plain call: identical ids in parity16; in the 16-bit
 modes (ids not pinned) the hidden rows along the common prefix within the mode's bound (2.5 % of their scale).
 
+`--rephrase W` (W > 0): the same with rephrase_weight = W, the [SEG] at the first answer index >= 2 whose id is new
+(a span that is not empty), `set_rephrase_paths` on for the five cases, and one more case, `plain_off`: the plain call with the
+switch off (today's behaviour, where a draft would be ignored), alternated with the others.
+
 Prints ONE JSON line: {"modes": {mode: {case: {ms_per_image: {median, min, max, rounds}, offered, accepted, decode_steps,
 verify_passes, over_plain, faster_than_plain_in_every_round}}}, ...}
 
-usage: python tools/ab_draft.py [--rounds 5] [--steps 10] [--warmup 3] [--modes perf,perf_int4w,parity16]
+usage: python tools/ab_draft.py [--rounds 5] [--steps 10] [--warmup 3] [--modes perf,perf_int4w,parity16] [--rephrase W]
 """
 import argparse
 import gc
@@ -48,7 +52,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10, help="generate calls per case and round")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--modes", default="perf")
+    ap.add_argument("--rephrase", type=float, default=0.0, help="rephrase_weight; > 0: the switch on, and the case plain_off")
     args = ap.parse_args()
+    reph = args.rephrase > 0
+    cases = CASES + ("plain_off",) if reph else CASES
     modes = tuple(args.modes.split(","))
     if any(m not in KNOWN for m in modes):
         raise SystemExit("ab_draft: --modes takes a comma-separated list of " + ", ".join(KNOWN))
@@ -57,6 +64,8 @@ def main():
     dev = torch.device("cuda", 0)
     cfg = config_7b()
     cfg.llm.max_seq = 512
+    if reph:
+        cfg.rephrase_weight = args.rephrase
     sd = synth_state_dict(cfg, seed=0, device=dev, round_bf16=False)
     sd = {k: v.half() if v.is_floating_point() else v for k, v in sd.items()}
     g = torch.Generator().manual_seed(1)
@@ -67,7 +76,9 @@ def main():
     sizes, H, W = [(1024, 1024)], [1024], [1024]
     V = cfg.llm.vocab
 
-    def run(m, draft, extras=False):
+    def run(m, draft, extras=False, case=None):
+        if reph:
+            m.set_rephrase_paths(case != "plain_off")
         return m.generate(clip, ids, sam, sizes, H, W, max_new_tokens=T_NEW, _return_extras=extras, draft_ids=draft)
 
     result = {}
@@ -75,7 +86,11 @@ def main():
         m = AnyRefForCausalLM.from_state_dict(cfg, sd, mode=mode, max_batch=1, max_seg=2)
         m.config.eos_token_id = None
         out_ids, _, _ = run(m, None)
-        m.set_seg_token_idx(int(out_ids[0, L + 2]))            # bench.py's rule: the id emitted at step 3 is [SEG]
+        seg_at = 2                                             # bench.py's rule: the id emitted at step 3 is [SEG]
+        if reph:                                               # ... or the first later id that is new: a span that is not empty
+            a0, old = out_ids[0, L:].tolist(), set(ids[0].tolist())
+            seg_at = next((i for i in range(2, T_NEW) if a0[i] not in old and a0[i] not in a0[:i]), 2)
+        m.set_seg_token_idx(int(out_ids[0, L + seg_at]))
         (out_ids, _, _), ex0 = run(m, None, True)
         answer = out_ids[0, L:].tolist()
 
@@ -84,11 +99,11 @@ def main():
             d[at] = (d[at] + 1) % V
             return [d]
 
-        drafts = dict(plain=None, full=[answer[:T_NEW - 1]], half=wrong(4), wrong1=wrong(1), wrong0=wrong(0))
+        drafts = dict(plain=None, full=[answer[:T_NEW - 1]], half=wrong(4), wrong1=wrong(1), wrong0=wrong(0), plain_off=None)
         slen = L + m.n_img - 1
         stats, checks = {}, {}
-        for case in CASES:                                     # untimed: counters and outputs
-            (o, _, _), ex = run(m, drafts[case], True)
+        for case in cases:                                     # untimed: counters and outputs
+            (o, _, _), ex = run(m, drafts[case], True, case)
             got = o[0, L:].tolist()
             stats[case] = dict(offered=int(ex["draft_offered"][0]), accepted=int(ex["draft_accepted"][0]),
                                decode_steps=ex["decode_steps"], verify_passes=ex["verify_passes"])
@@ -101,32 +116,35 @@ def main():
             if mode in PINNED:
                 assert same, f"{mode} / {case}: ids differ from the plain call: {got} vs {answer}"
             assert herr <= HIDDEN_REL * scale, f"{mode} / {case}: hidden err {herr} on a scale of {scale}"
-        for case in CASES:
+        for case in cases:
             for _ in range(args.warmup):
-                run(m, drafts[case])
+                run(m, drafts[case], case=case)
         torch.cuda.synchronize()
-        per = {case: [] for case in CASES}
+        per = {case: [] for case in cases}
         for r in range(args.rounds):
-            for case in (CASES if r % 2 == 0 else CASES[::-1]):
+            for case in (cases if r % 2 == 0 else cases[::-1]):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(args.steps):
-                    run(m, drafts[case])
+                    run(m, drafts[case], case=case)
                 torch.cuda.synchronize()
                 per[case].append((time.perf_counter() - t0) * 1e3 / args.steps)
-        med = {case: statistics.median(per[case]) for case in CASES}
+        med = {case: statistics.median(per[case]) for case in cases}
         result[mode] = {case: dict(
             ms_per_image=dict(median=round(med[case], 3), min=round(min(per[case]), 3), max=round(max(per[case]), 3),
                               rounds=[round(x, 3) for x in per[case]]),
             over_plain=round(med[case] / med["plain"], 4),
             faster_than_plain_in_every_round=all(a < b for a, b in zip(per[case], per["plain"])),
-            **stats[case], check=checks[case]) for case in CASES}
+            **stats[case], check=checks[case]) for case in cases}
+        if reph:
+            result[mode]["first_seg_span"] = answer.index(answer[seg_at])
+            result[mode]["plain_not_above_plain_off"] = med["plain"] <= med["plain_off"]
         del m
         gc.collect()
         torch.cuda.empty_cache()
     print(json.dumps(dict(
         workload="c2 (7B + ViT-L + SAM-H 1024^2, S 320, 10 new tokens), f16-rounded N(0, 0.02^2) weights, batch 1",
-        rounds=args.rounds, steps=args.steps, modes=result)), flush=True)
+        rounds=args.rounds, steps=args.steps, **(dict(rephrase_weight=args.rephrase) if reph else {}), modes=result)), flush=True)
 
 
 if __name__ == "__main__":

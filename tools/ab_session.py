@@ -12,12 +12,23 @@ Per mode the cases are timed alternately, round after round (`--rounds` x `--ste
 Before the timing, untimed, the session's answer is checked against the plain call's: identical ids in parity16; in the 16-bit
 modes (ids not pinned) the prompt's hidden rows within the mode's bound (2.5 % of their scale).
 
+`--rephrase W` (W > 0) runs the same workload with rephrase_weight = W, the [SEG] a few tokens into the answer (the
+first answer index >= 2 whose id is new, so the rephrased span is not empty), and these cases instead, the switch
+(`set_rephrase_paths`) set per case on the one handle:
+  plain          (a) plain call, switch off: today's behaviour, the baseline
+  plain_on       (b) plain call, switch on
+  query          (c) one session query            query4  (d) four queries in one call, per query
+  drafted_plain  (e) plain call with the answer as the draft       drafted  (f) (c) with that draft
+and times the tail alone at the C2 shape (e0 = 325, 32 heads, hd 128, span 9, bf16 cache): the per-image chain
+(anyref_op_rephrase_chain) against the fused pair (anyref_op_seg_rephrase), on events, alternated.
+
 `--plain-only` times (a) alone and needs nothing of the feature: with `--tree DIR` (a checkout of another commit, built) it is
 the parent's side of "the plain call costs what it cost".
 
 Prints ONE JSON line: {"modes": {mode: {case: {ms: {median, min, max, rounds}, ...}, query_below_plain_in_every_round}}, ...}
 
 usage: python tools/ab_session.py [--rounds 5] [--steps 10] [--warmup 3] [--modes perf,perf_int4w,parity16] [--plain-only] [--tree DIR]
+                                [--rephrase W]
 """
 import argparse
 import gc
@@ -61,6 +72,52 @@ def broadcast_alone(torch, cfg, P):
                 bytes_read_and_written=moved, gb_per_s=round(moved / statistics.median(ms) / 1e6, 1))
 
 
+def tail_alone(torch):
+    """the rephrase tail by itself at the C2 shape: one item, query row 325 over 326 keys of 32 heads x 128 in a bf16 cache, span
+    [316, 325), D = 4096.  Per round 20 launches of each form between two events, the two forms alternated; us per tail."""
+    import ctypes as C
+    from anyref_amd import _lib
+    lib = _lib.load()
+    S, H, hd, e0, s0 = 512, 32, 128, 325, 316
+    D = H * hd
+    q = torch.randn(1, S, H, hd, device="cuda").bfloat16()
+    k = torch.randn(1, S, H, hd, device="cuda").bfloat16()
+    hidden = torch.randn(1, S, D, device="cuda")
+    y = torch.zeros(1, D, device="cuda")
+    items = torch.tensor([[0, e0, s0, 0]], dtype=torch.int32, device="cuda")
+    scratch = torch.zeros(1, H, 16, device="cuda")
+    kvlen = torch.tensor([e0 + 1], dtype=torch.int32, device="cuda")
+    row = torch.zeros(S, device="cuda")
+    P = lambda t: C.c_void_p(t.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ok = C.c_int32(0)
+    scale = hd ** -0.5
+
+    def chain():
+        return lib.anyref_op_rephrase_chain(1, st, P(q), P(k), S, H, hd, P(hidden), 0, e0, s0, P(kvlen), P(row), scale, 0.1, P(y))
+
+    def pair():
+        return lib.anyref_op_seg_rephrase(1, st, P(q), P(k), S, H, hd, P(hidden), P(items), 1, e0 - s0, 16, P(scratch), scale, 0.1,
+                                          P(y), C.byref(ok))
+
+    us = dict(chain=[], pair=[])
+    for r in range(12):
+        for name, f in ((("chain", chain), ("pair", pair)) if r % 2 == 0 else (("pair", pair), ("chain", chain))):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(20):
+                assert f() == 0, lib.anyref_op_last_error().decode()
+            b.record()
+            torch.cuda.synchronize()
+            us[name].append(a.elapsed_time(b) * 1e3 / 20)
+    assert ok.value == 1
+    out = {n: dict(us_median=round(statistics.median(v[2:]), 2), us_min=round(min(v[2:]), 2), us_max=round(max(v[2:]), 2))
+           for n, v in us.items()}
+    out["shape"] = "e0 325, 32 heads x 128, span 9, bf16 cache; the chain's 4-byte upload is not in its time"
+    out["pair_not_above_chain"] = out["pair"]["us_median"] <= out["chain"]["us_median"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -69,6 +126,7 @@ def main():
     ap.add_argument("--modes", default="perf")
     ap.add_argument("--plain-only", action="store_true")
     ap.add_argument("--tree", default=ROOT, help="the checkout whose anyref_amd is measured")
+    ap.add_argument("--rephrase", type=float, default=0.0, help="rephrase_weight; > 0: the cases of DESIGN.md §8.9")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.tree))
     import torch
@@ -84,6 +142,9 @@ def main():
     dev = torch.device("cuda", 0)
     cfg = config_7b()
     cfg.llm.max_seq = 512
+    reph = args.rephrase > 0
+    if reph:
+        cfg.rephrase_weight = args.rephrase
     sd = synth_state_dict(cfg, seed=0, device=dev, round_bf16=False)
     sd = {k: v.half() if v.is_floating_point() else v for k, v in sd.items()}
     g = torch.Generator().manual_seed(1)
@@ -95,6 +156,8 @@ def main():
     L = full.shape[1]
     sizes, H, W = [(1024, 1024)], [1024], [1024]
     cases = ("plain",) if args.plain_only else ("plain", "open", "query", "query4", "drafted")
+    if reph and not args.plain_only:
+        cases = ("plain", "plain_on", "query", "query4", "drafted_plain", "drafted")
 
     result = {}
     for mode in modes:
@@ -102,7 +165,11 @@ def main():
         m.config.eos_token_id = None
         plain = lambda extras=False: m.generate(clip, full, sam, sizes, H, W, max_new_tokens=T_NEW, _return_extras=extras)
         out_ids, _, _ = plain()
-        m.set_seg_token_idx(int(out_ids[0, L + 2]))            # bench.py's rule: the id emitted at step 3 is [SEG]
+        seg_at = 2                                             # bench.py's rule: the id emitted at step 3 is [SEG]
+        if reph:                                               # ... or the first later id that is new: a span that is not empty
+            a0, old = out_ids[0, L:].tolist(), set(full[0].tolist())
+            seg_at = next((i for i in range(2, T_NEW) if a0[i] not in old and a0[i] not in a0[:i]), 2)
+        m.set_seg_token_idx(int(out_ids[0, L + seg_at]))
         (out_ids, _, _), ex0 = plain(True)
         answer = out_ids[0, L:].tolist()
         P = len(prefix) + m.n_img - 1
@@ -115,7 +182,12 @@ def main():
         run = dict(plain=lambda: plain(), open=reopen,
                    query=lambda: sess[0].generate(suffixes[:1], max_new_tokens=T_NEW),
                    query4=lambda: sess[0].generate(suffixes, max_new_tokens=T_NEW),
-                   drafted=lambda: sess[0].generate(suffixes[:1], max_new_tokens=T_NEW, draft_ids=[answer[:T_NEW - 1]]))
+                   drafted=lambda: sess[0].generate(suffixes[:1], max_new_tokens=T_NEW, draft_ids=[answer[:T_NEW - 1]]),
+                   plain_on=lambda: plain(),
+                   drafted_plain=lambda: m.generate(clip, full, sam, sizes, H, W, max_new_tokens=T_NEW,
+                                                    draft_ids=[answer[:T_NEW - 1]]))
+        if reph and not args.plain_only:
+            m.set_rephrase_paths(True)
         if not args.plain_only:                                # untimed: the session's answer against the plain call's
             reopen()
             for case, rows, draft in (("query", suffixes[:1], None), ("query4", suffixes, None),
@@ -133,6 +205,8 @@ def main():
                 assert herr <= HIDDEN_REL * scale, f"{mode} / {case}: hidden err {herr} on a scale of {scale}"
 
         def prepare(case):                                     # a session query needs an open session; plain ends it
+            if reph and not args.plain_only:
+                m.set_rephrase_paths(case != "plain")
             if case in ("query", "query4", "drafted"):
                 reopen()
                 run[case]()                                    # (query4: the broadcast happens once per session, here)
@@ -162,12 +236,16 @@ def main():
             **({"check": check[case]} if case in check else {})) for case in cases}
         if not args.plain_only:
             result[mode]["query_below_plain_in_every_round"] = all(a < b for a, b in zip(per["query"], per["plain"]))
+        if reph:
+            result[mode]["seg_at_answer_index"] = seg_at
+            result[mode]["first_seg_span"] = answer.index(answer[seg_at])
         del m
         gc.collect()
         torch.cuda.empty_cache()
     bcast = None if args.plain_only else broadcast_alone(torch, cfg, len(prefix) + cfg.clip.n_patches - 1)
     print(json.dumps(dict(
-        broadcast_alone=bcast,
+        broadcast_alone=bcast, **(dict(rephrase_weight=args.rephrase, tail_alone=None if args.plain_only else tail_alone(torch))
+                                  if reph else {}),
         workload="c2 (7B + ViT-L + SAM-H 1024^2, prefix 291 rows + question 29 = S 320, 10 new tokens), f16-rounded N(0, 0.02^2) "
                  "weights, one handle per mode with max_batch 4; query4 is per query",
         tree=os.path.relpath(os.path.abspath(args.tree), ROOT), plain_only=args.plain_only, rounds=args.rounds, steps=args.steps,
