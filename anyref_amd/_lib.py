@@ -77,6 +77,15 @@ class AttnEx(C.Structure):
                                           "max_wg")] +
                 [("scale", _F)])
 
+class LoraPair(C.Structure):
+    """anyref_lora_pair (include/anyref_hip.h)"""
+    _fields_ = [("weight_name", C.c_char_p), ("A", _P), ("B", _P), ("r", C.c_int32), ("is_device", C.c_int32),
+                ("transposed", C.c_int32)]
+
+
+# projection bits of anyref_adapter_reserve (ANYREF_LORA_*)
+LORA_Q, LORA_K, LORA_V, LORA_O, LORA_GATE, LORA_UP, LORA_DOWN = 1, 2, 4, 8, 16, 32, 64
+
 # name -> (restype, argtypes): every symbol the two headers declare
 SYMBOLS = {
     "anyref_create": (_I, [C.POINTER(AnyrefConfig), _I, C.POINTER(_P)]),
@@ -98,6 +107,10 @@ SYMBOLS = {
     "anyref_session_open": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
     "anyref_session_generate": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
     "anyref_session_close": (_I, [_P]),
+    "anyref_adapter_reserve": (_I, [_P, C.c_uint32]),
+    "anyref_adapter_apply": (_I, [_P, _P, _P, _I, _F]),
+    "anyref_update_weight": (_I, [_P, _P, C.c_char_p, _P, _I, _I, C.POINTER(_L), _I]),
+    "anyref_adapter_stats": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_L), C.POINTER(C.c_double)]),
     "anyref_project_audio": (_I, [_P, _P, _P, _I, _P]),
     "anyref_audio_encode": (_I, [_P, _P, _P, _I, _P]),
     "anyref_seg_tail": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _L, _P, _P]),
@@ -130,6 +143,7 @@ SYMBOLS = {
     "anyref_op_quant_fp8": (_I, [_P, _P, _I, _I, _P, _P]),
     "anyref_op_gemv_fp8": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     "anyref_op_quant_int4": (_I, [_P, _P, _I, _I, _P, _P]),
+    "anyref_op_lora_merge": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _I, _F, _P, _I, _I, _P]),
     "anyref_op_dequant_int4": (_I, [_P, _P, _P, _I, _I, _P]),
     "anyref_op_gemm_int4": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "anyref_op_gemv_int4": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I]),

@@ -141,10 +141,13 @@ def _strip_peft_key(k: str) -> str:
     return k.replace(".modules_to_save.default", "").replace(".modules_to_save", "").replace(".default", "")
 
 
-def merge_lora(sd: Dict[str, torch.Tensor], adapter_dir: str) -> Dict[str, int]:
-    """`PeftModel.from_pretrained(model, dir).merge_and_unload()` on a flat state dict (peft 0.4.0 file layout:
-    `adapter_config.json` + `adapter_model.bin|safetensors`).  LoRA pairs: W += (lora_alpha / r) * B @ A (transposed
-    when `fan_in_fan_out`); `modules_to_save` tensors replace the base ones.  Returns counts for the log."""
+def read_adapter(adapter_dir: str, base_names=None):
+    """The parsing half of `merge_lora`: a peft 0.4.0 adapter directory (`adapter_config.json` +
+    `adapter_model.bin|safetensors`) -> `(pairs, saved, scaling, fan_in_fan_out)`.  `pairs` maps a module name
+    (`model.layers.0.self_attn.q_proj`) to its `(lora_A, lora_B)` tensors as stored, `saved` maps the reference names of the
+    `modules_to_save` tensors to theirs, `scaling = lora_alpha / r`.  Raises as `merge_lora` always did: unpaired tensors, an
+    adapter tensor that is no Linear LoRA pair, a rank that is not `adapter_config.json`'s; with `base_names` (the names of the
+    base weights) also a target the base does not have."""
     ac = json.load(open(os.path.join(adapter_dir, "adapter_config.json")))
     r, alpha = int(ac["r"]), float(ac["lora_alpha"])
     scaling = alpha / r
@@ -171,13 +174,49 @@ def merge_lora(sd: Dict[str, torch.Tensor], adapter_dir: str) -> Dict[str, int]:
             saved[k] = v
     if set(A) != set(B):
         raise ValueError("adapter has unpaired lora_A / lora_B tensors")
+    pairs = {}
     for mod in A:
         name = mod + ".weight"
-        if name not in sd:
+        if base_names is not None and name not in base_names:
             raise KeyError(f"adapter targets {name}, which the base checkpoint does not have")
-        a, b = A[mod].float(), B[mod].float()
+        a, b = A[mod], B[mod]
         if a.shape[0] != r or b.shape[1] != r:
             raise ValueError(f"{mod}: LoRA rank {a.shape[0]} / {b.shape[1]} != r = {r} of adapter_config.json")
+        pairs[mod] = (a, b)
+    return pairs, saved, scaling, fifo
+
+
+def check_adapter_shapes(pairs, saved, shapes, fan_in_fan_out: bool = False):
+    """An adapter read by `read_adapter` against the shapes a model was built with (`shapes`: reference name -> shape): every
+    LoRA pair must multiply out to its target's shape and every `modules_to_save` tensor must have the built one -- a
+    vocabulary that differs is named with both sizes (it cannot change after the build)."""
+    for mod, (a, b) in pairs.items():
+        name = mod + ".weight"
+        if name not in shapes:
+            raise KeyError(f"adapter targets {name}, which the base checkpoint does not have")
+        n, k = (int(v) for v in shapes[name])
+        got = (int(a.shape[1]), int(b.shape[0])) if fan_in_fan_out else (int(b.shape[0]), int(a.shape[1]))
+        if got != (n, k):
+            raise ValueError(f"{mod}: the LoRA pair makes a {got[0]} x {got[1]} update, the built weight is {n} x {k}")
+    for k, v in saved.items():
+        if k not in shapes:
+            raise KeyError(f"adapter saves {k}, which the built model does not have")
+        want = tuple(int(x) for x in shapes[k])
+        if tuple(v.shape) != want:
+            if k in ("model.embed_tokens.weight", "lm_head.weight") and v.dim() == 2 and v.shape[0] != want[0]:
+                raise ValueError(f"{k}: the adapter was trained with a vocabulary of {v.shape[0]}, the model was built for "
+                                 f"{want[0]} (resize_token_embeddings before the build; the vocabulary cannot change after it)")
+            raise ValueError(f"{k}: the adapter holds shape {tuple(v.shape)}, the model was built with {want}")
+
+
+def merge_lora(sd: Dict[str, torch.Tensor], adapter_dir: str) -> Dict[str, int]:
+    """`PeftModel.from_pretrained(model, dir).merge_and_unload()` on a flat state dict (peft 0.4.0 file layout:
+    `adapter_config.json` + `adapter_model.bin|safetensors`).  LoRA pairs: W += (lora_alpha / r) * B @ A (transposed
+    when `fan_in_fan_out`); `modules_to_save` tensors replace the base ones.  Returns counts for the log."""
+    pairs, saved, scaling, fifo = read_adapter(adapter_dir, base_names=sd)
+    for mod, (a, b) in pairs.items():
+        name = mod + ".weight"
+        a, b = a.float(), b.float()
         delta = (b @ a) * scaling
         if fifo:
             delta = delta.t()
@@ -185,7 +224,7 @@ def merge_lora(sd: Dict[str, torch.Tensor], adapter_dir: str) -> Dict[str, int]:
         sd[name] = (w.float() + delta).to(w.dtype)
     for k, v in saved.items():
         sd[k] = v
-    return {"lora_pairs": len(A), "modules_to_save": len(saved)}
+    return {"lora_pairs": len(pairs), "modules_to_save": len(saved)}
 
 
 def missing_for(cfg: AnyRefConfig, names: Iterable[str], audio: bool) -> list:

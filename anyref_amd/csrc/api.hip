@@ -140,6 +140,22 @@ int anyref_draft_stats(anyref_handle* h, int32_t* offered, int32_t* accepted, in
   GUARD(h, h->m->draft_stats(offered, accepted, B, decode_steps, verify_passes));
 }
 
+int anyref_adapter_reserve(anyref_handle* h, uint32_t targets) { GUARD(h, h->m->adapter_reserve(targets)); }
+
+int anyref_adapter_apply(anyref_handle* h, void* stream, const anyref_lora_pair* pairs, int n_pairs, float scaling) {
+  GUARD(h, h->m->adapter_apply((hipStream_t)stream, pairs, n_pairs, scaling));
+}
+
+int anyref_update_weight(anyref_handle* h, void* stream, const char* name, const void* ptr, int is_device, int dtype,
+                         const int64_t* shape, int ndim) {
+  GUARD(h, h->m->update_weight((hipStream_t)stream, name, ptr, is_device, dtype, shape, ndim));
+}
+
+int anyref_adapter_stats(anyref_handle* h, int32_t* targets_reserved, int32_t* pairs_active, int64_t* inexact,
+                         double* last_apply_ms) {
+  GUARD(h, h->m->adapter_stats(targets_reserved, pairs_active, inexact, last_apply_ms));
+}
+
 int anyref_audio_encode(anyref_handle* h, void* stream, const float* mel, int n, float* emb) {
   GUARD(h, h->m->audio_encode((hipStream_t)stream, mel, n, emb));
 }

@@ -230,6 +230,13 @@ void launch_quant_int4_rows(const float* src, int lds, int N, int K, uint8_t* q,
 // q * s -> bf16 [N, K] (prefill GEMM operand); every element exact by construction
 void launch_dequant_int4_rows(const uint8_t* q, int ldq, const void* scale_bf16, int ld_scale, int N, int K, void* out_bf16,
                               int ldo, hipStream_t s);
+// LoRA merge into a packed weight buffer (lora.hip; the rule: anyref_amd/lora.py): dst[n * row_stride, k] = W(d_in(f32(f64 sum_j
+// B[n,j] A[j,k] * scaling + base[n,k]))) for k < K; base f32 [N, K] contiguous, A f32 [r, K], B f32 [N, r], r in 0 .. 64 (0: the base
+// as finalize converts it), dst rows `ld` elements apart (row_stride 1 or 2: every second row), pad columns untouched.
+// counts (optional, 16-bit W): [0] += inexact elements, [1] += finite values stored as inf.  `name` goes into the error texts.
+template <typename W>
+void launch_lora_merge(const float* base, int d_in, int N, int K, const float* A, const float* B, int r, float scaling,
+                       void* dst, int64_t ld, int row_stride, unsigned long long* counts, hipStream_t s, const char* name);
 // the decode GEMV on int4 weights (GemvArgs::w_int4): 1 - 4 batch rows per pass
 void launch_gemv_int4(const GemvArgs& a, hipStream_t s);
 

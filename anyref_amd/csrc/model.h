@@ -13,6 +13,7 @@ namespace anyref {
 
 struct RawTensor {
   float* p = nullptr;  // f32 device copy
+  int dtype = ANYREF_F32;  // the type it was handed to set_weight in (every such value is exact in the f32 copy)
   std::vector<int64_t> shape;
   int64_t numel() const {
     int64_t n = 1;
@@ -67,6 +68,33 @@ class ModelBase {
     if (sess_live_) sess_lost_by_ = by;
     sess_live_ = false;
   }
+  // ---- adapter hot-swap (anyref_adapter_*) ----
+  // before finalize: the LLaMA linears named by `targets` (ANYREF_LORA_* bits) keep their raw f32 tensor past finalize
+  void adapter_reserve(uint32_t targets) {
+    if (finalized_) throw std::runtime_error("anyref_adapter_reserve after anyref_finalize: reserve before the weights are packed");
+    if (targets == 0 || (targets & ~(uint32_t)ANYREF_LORA_ALL))
+      throw std::runtime_error("anyref_adapter_reserve: targets must be a non-empty mask of ANYREF_LORA_* bits");
+    resv_mask_ = targets;
+  }
+  virtual void adapter_apply(hipStream_t s, const anyref_lora_pair* pairs, int n_pairs, float scaling) = 0;
+  virtual void update_weight(hipStream_t s, const char* name, const void* ptr, int is_device, int dtype, const int64_t* shape,
+                             int ndim) = 0;
+  void adapter_stats(int32_t* targets_reserved, int32_t* pairs_active, int64_t* inexact, double* last_apply_ms) const {
+    if (targets_reserved) *targets_reserved = (int32_t)lora_targets_.size();
+    if (pairs_active) *pairs_active = pairs_active_;
+    if (inexact) *inexact = inexact_weights();
+    if (last_apply_ms) *last_apply_ms = last_apply_ms_;
+  }
+  // one reserved LoRA target: the unmerged base (the raw tensor finalize would have freed) and where its packed rows live
+  struct LoraTarget {
+    std::string name;
+    float* base = nullptr;  // f32 [N, K], owned (tracked in allocs_)
+    int d_in = ANYREF_F32;  // dtype it was handed over in
+    int N = 0, K = 0;
+    int layer = 0, kind = 0;  // kind: bit index of ANYREF_LORA_* (q k v o gate up down)
+    int r = 0;                // rank merged into the packed rows now (0: the base)
+    int64_t inexact = 0;      // elements of the packed rows that are not exactly the merged value
+  };
   virtual void project_audio(hipStream_t s, const float* audio_emb, int n, float* out) = 0;
   virtual void audio_encode(hipStream_t s, const float* mel, int n, float* emb) = 0;
   virtual void seg_tail(hipStream_t s, const float* sam_images, const int64_t* ids, const int32_t* ids_lens,
@@ -162,6 +190,11 @@ class ModelBase {
   unsigned long long* weight_counts();
   void close_weight_counts();
   int64_t inexact_ = 0;
+  uint32_t resv_mask_ = 0;  // adapter_reserve
+  std::vector<LoraTarget> lora_targets_;
+  std::map<std::string, int64_t> upd_inexact_;  // inexact elements of the tensors anyref_update_weight can replace (reserving handles)
+  int pairs_active_ = 0;
+  double last_apply_ms_ = 0.0;
   bool overlap_ = true;
   bool use_graphs_ = true;
   bool reph_paths_ = false;   // set_rephrase_paths

@@ -69,6 +69,7 @@ void ModelBase::set_weight(const char* name, const void* ptr, int is_device, int
   HIP_TRY(hipSetDevice(device_));
   if (finalized_) throw std::runtime_error("set_weight after finalize");
   RawTensor t;
+  t.dtype = dtype;
   t.shape.assign(shape, shape + ndim);
   const int64_t n = t.numel();
   const size_t esz = dtype == ANYREF_F32 ? 4 : 2;
@@ -214,6 +215,8 @@ class Model : public ModelBase {
     if (ext_stage_) (void)hipHostFree(ext_stage_);
     if (drf_host_) (void)hipHostFree(drf_host_);
     if (ext_ev_) (void)hipEventDestroy(ext_ev_);
+    for (auto e : lora_ev_)
+      if (e) (void)hipEventDestroy(e);
     for (auto e : ev_tok_)
       if (e) (void)hipEventDestroy(e);
     for (auto e : stage_ev_)
@@ -260,6 +263,9 @@ class Model : public ModelBase {
                         int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
                         int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) override;
   void join_sam_public(hipStream_t s) { join_sam(s); }
+  void adapter_apply(hipStream_t s, const anyref_lora_pair* pairs, int n_pairs, float scaling) override;
+  void update_weight(hipStream_t s, const char* name, const void* ptr, int is_device, int dtype, const int64_t* shape,
+                     int ndim) override;
 
  private:
   // ---- packing helpers ----
@@ -269,6 +275,38 @@ class Model : public ModelBase {
   template <typename E>
   E* pack_rows(E* dst, int dst_row0, const std::string& name, int rows, int cols, int kpad);
   void check_f16_range(const std::string& name);
+  // ---- adapter hot-swap ----
+  struct LoraJob {  // one reserved target's rewrite: A / B on the device, r = 0 for the base
+    int target = 0;
+    const float* A = nullptr;
+    const float* B = nullptr;
+    int r = 0;
+  };
+  void lora_write(hipStream_t s, const LoraTarget& tg, const float* A, const float* B, int r, float scaling,
+                  unsigned long long* counts);
+  // runs the jobs between a hipEvent pair, books each target's counters; throws (targets back at the base) on an f16 overflow
+  void lora_run(hipStream_t s, const std::vector<LoraJob>& jobs, float scaling);
+  void adapter_setup();  // end of finalize on a reserving handle: counters, scratch, and each target's inexact count
+  // packing of a tensor finalize counts on its own when the handle reserves (anyref_update_weight can replace it later)
+  template <typename F>
+  void counted_pack(const std::string& name, F&& pack) {
+    if (!resv_mask_) return pack();
+    unsigned long long c0 = 0, c1 = 0;
+    HIP_TRY(hipStreamSynchronize(0));
+    HIP_TRY(hipMemcpy(&c0, weight_counts(), sizeof(c0), hipMemcpyDeviceToHost));
+    pack();
+    HIP_TRY(hipStreamSynchronize(0));
+    HIP_TRY(hipMemcpy(&c1, weight_counts(), sizeof(c1), hipMemcpyDeviceToHost));
+    upd_inexact_[name] = (int64_t)(c1 - c0);
+  }
+  static std::vector<float> convt_reorder_w(const std::vector<float>& w, int cin, int cout);  // [cin][cout][2][2] -> [(dy*2+dx)*cout+co][ci]
+  static std::vector<float> convt_reorder_b(const std::vector<float>& b, int cout);
+  unsigned long long* lora_counts_ = nullptr;  // [targets][2] device
+  float* lora_scratch_ = nullptr;              // fp8 / int4 weights: the merged f32 rows of one target
+  float* lora_stage_ = nullptr;                // A / B handed over in host memory (or transposed), for the length of one apply
+  size_t lora_stage_cap_ = 0;
+  hipEvent_t lora_ev_[2] = {nullptr, nullptr};
+  int64_t fixed_inexact_ = 0;                  // inexact elements of everything no adapter call can rewrite
   template <typename E = W>
   Lin<E> pack_linear(const std::string& wname, const std::string& bname, int n, int k, int kalign = 8,
                      int rowpad = 0);
@@ -382,8 +420,13 @@ class Model : public ModelBase {
     const RawTensor& t = raw(name);
     if (t.numel() != (int64_t)rows * cols || cols != l.k)
       throw std::runtime_error("shape mismatch for " + name + " (fp8 pack)");
-    launch_quant_fp8_rows(t.p, cols, rows, cols, l.w8 + (size_t)row0 * l.stride(), l.stride() * rstride, l.ws + row0, 0,
-                          rstride, weight_counts());
+    pack_src_fp8(l, row0, t.p, rows, cols, rstride, 0, weight_counts());
+  }
+  // the same from any f32 [rows, cols] device tensor (finalize: the raw tensor; adapter paths: the merged / replaced rows)
+  void pack_src_fp8(Lin<W>& l, int row0, const float* src, int rows, int cols, int rstride, hipStream_t s,
+                    unsigned long long* counts) {
+    launch_quant_fp8_rows(src, cols, rows, cols, l.w8 + (size_t)row0 * l.stride(), l.stride() * rstride, l.ws + row0, s, rstride,
+                          counts);
   }
   Lin<W> alloc_fp8(int n, int k) {
     if (k % 16) throw std::runtime_error("fp8 weights need K % 16 == 0");
@@ -402,8 +445,12 @@ class Model : public ModelBase {
     const RawTensor& t = raw(name);
     if (t.numel() != (int64_t)rows * cols || cols != l.k)
       throw std::runtime_error("shape mismatch for " + name + " (int4 pack)");
-    launch_quant_int4_rows(t.p, cols, rows, cols, l.w4 + (size_t)row0 * l.ld4, l.ld4 * rstride, l.s4 + (size_t)row0 * l.ng4,
-                           l.ng4 * rstride, 0, weight_counts());
+    pack_src_int4(l, row0, t.p, rows, cols, rstride, 0, weight_counts());
+  }
+  void pack_src_int4(Lin<W>& l, int row0, const float* src, int rows, int cols, int rstride, hipStream_t s,
+                     unsigned long long* counts) {
+    launch_quant_int4_rows(src, cols, rows, cols, l.w4 + (size_t)row0 * l.ld4, l.ld4 * rstride, l.s4 + (size_t)row0 * l.ng4,
+                           l.ng4 * rstride, s, counts);
   }
   Lin<W> alloc_int4(int n, int k, const std::string& name) {
     if (k % 16) throw std::runtime_error("int4 weights need K % 16 == 0: " + name + " has K = " + std::to_string(k));
@@ -878,7 +925,7 @@ void Model<T, TS>::finalize() {
       throw std::runtime_error("embed_tokens shape mismatch (vocab/dim)");
     if (SPT && H % 64) throw std::runtime_error("parity16: llm_dim must be a multiple of 64");
     emb_table_ = talloc<W>((size_t)V * H);
-    pack_rows(emb_table_, 0, "model.embed_tokens.weight", V, H, H);
+    counted_pack("model.embed_tokens.weight", [&] { pack_rows(emb_table_, 0, "model.embed_tokens.weight", V, H, H); });
     llm_layers_.resize(c.llm_layers);
     for (int i = 0; i < c.llm_layers; ++i) {
       const std::string lp = "model.layers." + std::to_string(i) + ".";
@@ -921,24 +968,37 @@ void Model<T, TS>::finalize() {
       }
       // free the raw copies of this layer early (7B in f32 is 27 GB)
       HIP_TRY(hipStreamSynchronize(0));
-      for (const char* nm : {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
-                             "self_attn.o_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight",
-                             "mlp.down_proj.weight"}) {
-        auto it = raw_.find(lp + nm);
-        if (it != raw_.end()) {
+      // (a reserved LoRA target keeps its tensor instead: ownership moves to lora_targets_, no copy)
+      const char* lin_names[7] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
+                                  "self_attn.o_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight",
+                                  "mlp.down_proj.weight"};
+      for (int j = 0; j < 7; ++j) {
+        auto it = raw_.find(lp + lin_names[j]);
+        if (it == raw_.end()) continue;
+        if (resv_mask_ >> j & 1u) {
+          LoraTarget tg;
+          tg.name = it->first;
+          tg.base = it->second.p;
+          tg.d_in = it->second.dtype;
+          tg.N = j == 4 || j == 5 ? F : H;
+          tg.K = j == 6 ? F : H;
+          tg.layer = i;
+          tg.kind = j;
+          lora_targets_.push_back(tg);
+        } else {
           dfree(it->second.p);
-          raw_.erase(it);
         }
+        raw_.erase(it);
       }
     }
     llm_norm_ = affine("model.norm", false);
     if (fp8w_) {
       lm_head_ = alloc_fp8(V, H);
-      pack_rows_fp8(lm_head_, 0, "lm_head.weight", V, H);
+      counted_pack("lm_head.weight", [&] { pack_rows_fp8(lm_head_, 0, "lm_head.weight", V, H); });
       const size_t big = std::max((size_t)2 * F * H, std::max((size_t)3 * H * H, (size_t)V * H));
       deq_buf_ = talloc<W>(big);
     } else {
-      lm_head_ = pack_linear("lm_head.weight", "", V, H, 8, kRowPadBytes / (int)sizeof(W));
+      counted_pack("lm_head.weight", [&] { lm_head_ = pack_linear("lm_head.weight", "", V, H, 8, kRowPadBytes / (int)sizeof(W)); });
       // int4: lm_head stays bf16.  The GEMM multiplies the nibbles as stored; only a linear with K % 64 != 0 goes through a
       // bf16 image, sized to the largest such linear (none at 7B / 13B widths: no buffer)
       if (int4w_) {
@@ -1002,7 +1062,9 @@ void Model<T, TS>::finalize() {
     fc2_ = pack_linear_f32("model.text_hidden_fcs.0.2.weight", "model.text_hidden_fcs.0.2.bias", c.out_dim, H);
     has_audio_ = has_raw("model.audio_projector.weight");
     if (has_audio_)
-      audio_proj_ = pack_linear("model.audio_projector.weight", "model.audio_projector.bias", H, c.audio_dim);
+      counted_pack("model.audio_projector.weight", [&] {
+        audio_proj_ = pack_linear("model.audio_projector.weight", "model.audio_projector.bias", H, c.audio_dim);
+      });
     const size_t ns = (size_t)MB * c.max_seg;
     seg_h_ = talloc<float>(ns * H);
     seg_t_ = talloc<float>(ns * H);
@@ -1152,12 +1214,7 @@ void Model<T, TS>::finalize() {
     auto convT = [&](const std::string& name, int cin, int cout) {  // [cin][cout][2][2] -> [(dy*2+dx)*cout+co][ci]
       std::vector<float> w = to_host(name + ".weight"), bsrc = to_host(name + ".bias");
       if ((int)w.size() != cin * cout * 4 || (int)bsrc.size() != cout) throw std::runtime_error("convT shape " + name);
-      std::vector<float> r((size_t)4 * cout * cin), rb((size_t)4 * cout);
-      for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < cout; ++co)
-          for (int t = 0; t < 4; ++t) r[((size_t)t * cout + co) * cin + ci] = w[((size_t)ci * cout + co) * 4 + t];
-      for (int t = 0; t < 4; ++t)
-        for (int co = 0; co < cout; ++co) rb[(size_t)t * cout + co] = bsrc[co];
+      const std::vector<float> r = convt_reorder_w(w, cin, cout), rb = convt_reorder_b(bsrc, cout);
       LinF l;
       l.n = 4 * cout;
       l.k = cin;
@@ -1277,6 +1334,311 @@ void Model<T, TS>::finalize() {
   close_weight_counts();
   drop_raw();
   finalized_ = true;
+  if (!lora_targets_.empty()) adapter_setup();
+}
+
+// ---------------------------------------------------------------------------------------------
+// adapter hot-swap (anyref_adapter_apply / anyref_update_weight)
+// ---------------------------------------------------------------------------------------------
+template <typename T, typename TS>
+std::vector<float> Model<T, TS>::convt_reorder_w(const std::vector<float>& w, int cin, int cout) {
+  std::vector<float> r((size_t)4 * cout * cin);
+  for (int ci = 0; ci < cin; ++ci)
+    for (int co = 0; co < cout; ++co)
+      for (int t = 0; t < 4; ++t) r[((size_t)t * cout + co) * cin + ci] = w[((size_t)ci * cout + co) * 4 + t];
+  return r;
+}
+template <typename T, typename TS>
+std::vector<float> Model<T, TS>::convt_reorder_b(const std::vector<float>& b, int cout) {
+  std::vector<float> rb((size_t)4 * cout);
+  for (int t = 0; t < 4; ++t)
+    for (int co = 0; co < cout; ++co) rb[(size_t)t * cout + co] = b[co];
+  return rb;
+}
+
+// one target's packed rows <- W(rule(base, A, B, r, scaling)); r = 0: the base as finalize converted it
+template <typename T, typename TS>
+void Model<T, TS>::lora_write(hipStream_t s, const LoraTarget& tg, const float* A, const float* B, int r, float scaling,
+                              unsigned long long* counts) {
+  LlmLayer& L = llm_layers_[tg.layer];
+  const int H = cfg.llm_dim;
+  Lin<W>* l = nullptr;
+  int row0 = 0, rs = 1;
+  switch (tg.kind) {
+    case 0: l = &L.qkv; break;
+    case 1: l = &L.qkv; row0 = H; break;
+    case 2: l = &L.qkv; row0 = 2 * H; break;
+    case 3: l = &L.o; break;
+    case 4: l = &L.gu; rs = 2; break;             // rows interleaved: 2j = gate_j
+    case 5: l = &L.gu; row0 = 1; rs = 2; break;   //                   2j + 1 = up_j
+    default: l = &L.down; break;
+  }
+  if (l->w4 || l->w8) {  // the merged f32 rows, then the quantiser finalize runs
+    launch_lora_merge<float>(tg.base, tg.d_in, tg.N, tg.K, A, B, r, scaling, lora_scratch_, tg.K, 1, nullptr, s, tg.name.c_str());
+    if (l->w4) pack_src_int4(*l, row0, lora_scratch_, tg.N, tg.K, rs, s, counts);
+    else pack_src_fp8(*l, row0, lora_scratch_, tg.N, tg.K, rs, s, counts);
+  } else {
+    launch_lora_merge<W>(tg.base, tg.d_in, tg.N, tg.K, A, B, r, scaling, l->w + (size_t)row0 * l->stride(), l->stride(), rs, counts,
+                         s, tg.name.c_str());
+  }
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::lora_run(hipStream_t s, const std::vector<LoraJob>& jobs, float scaling) {
+  const size_t nt = lora_targets_.size();
+  HIP_TRY(hipMemsetAsync(lora_counts_, 0, nt * 2 * sizeof(unsigned long long), s));
+  HIP_TRY(hipEventRecord(lora_ev_[0], s));
+  for (const LoraJob& j : jobs) lora_write(s, lora_targets_[j.target], j.A, j.B, j.r, scaling, lora_counts_ + 2 * j.target);
+  HIP_TRY(hipEventRecord(lora_ev_[1], s));
+  HIP_TRY(hipEventSynchronize(lora_ev_[1]));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, lora_ev_[0], lora_ev_[1]));
+  last_apply_ms_ = ms;
+  std::vector<unsigned long long> h(nt * 2);
+  HIP_TRY(hipMemcpy(h.data(), lora_counts_, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  std::string over;
+  for (const LoraJob& j : jobs) {
+    LoraTarget& tg = lora_targets_[j.target];
+    tg.r = j.r;
+    tg.inexact = (int64_t)h[2 * j.target];
+    if (F16W && h[2 * j.target + 1] && over.empty())
+      over = tg.name + ": " + std::to_string(h[2 * j.target + 1]) + " merged weight(s) outside the f16 range (|w| > 65504)";
+  }
+  if (!over.empty()) {  // an inf must not stay in the weights: every target this call merged returns to its base (the
+    std::vector<LoraJob> back;  // targets it did not name were r = 0 jobs already)
+    for (const LoraJob& j : jobs)
+      if (j.r) back.push_back(LoraJob{j.target, nullptr, nullptr, 0});
+    lora_run(s, back, 0.f);
+  }
+  pairs_active_ = 0;
+  inexact_ = fixed_inexact_;
+  for (const LoraTarget& tg : lora_targets_) {
+    pairs_active_ += tg.r ? 1 : 0;
+    inexact_ += tg.inexact;
+  }
+  for (const auto& kv : upd_inexact_) inexact_ += kv.second;
+  if (!over.empty()) throw std::runtime_error(over + "; the reserved targets are back at their base");
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::adapter_setup() {
+  const size_t nt = lora_targets_.size();
+  lora_counts_ = talloc<unsigned long long>(nt * 2);
+  if (fp8w_ || int4w_) {
+    size_t big = 0;
+    for (const LoraTarget& tg : lora_targets_) big = std::max(big, (size_t)tg.N * tg.K);
+    lora_scratch_ = talloc<float>(big);
+  }
+  for (auto& e : lora_ev_) HIP_TRY(hipEventCreate(&e));
+  // One pass of the merge kernel at r = 0 over every target: the bits finalize stored, and each target's own inexact count
+  // (finalize keeps one sum).  What is left of that sum belongs to tensors no adapter call rewrites.
+  const int64_t total = inexact_;
+  fixed_inexact_ = 0;
+  std::vector<LoraJob> jobs;
+  for (size_t i = 0; i < nt; ++i) jobs.push_back(LoraJob{(int)i, nullptr, nullptr, 0});
+  lora_run(0, jobs, 0.f);
+  int64_t mine = 0;
+  for (const LoraTarget& tg : lora_targets_) mine += tg.inexact;
+  for (const auto& kv : upd_inexact_) mine += kv.second;
+  fixed_inexact_ = total - mine;
+  inexact_ = total;
+  last_apply_ms_ = 0.0;
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::adapter_apply(hipStream_t s, const anyref_lora_pair* pairs, int n_pairs, float scaling) {
+  HIP_TRY(hipSetDevice(device_));
+  if (!finalized_) throw std::runtime_error("anyref_adapter_apply before anyref_finalize");
+  if (lora_targets_.empty())
+    throw std::runtime_error("anyref_adapter_apply: this handle reserved no LoRA targets (anyref_adapter_reserve before "
+                             "anyref_finalize; adapters= in Python)");
+  if (n_pairs < 0 || (n_pairs > 0 && !pairs)) throw std::runtime_error("anyref_adapter_apply: bad pairs / n_pairs");
+  if (n_pairs > 0 && (!(scaling == scaling) || scaling - scaling != 0.f))
+    throw std::runtime_error("anyref_adapter_apply: scaling is not finite");
+  // ---- validate everything before anything is written ----
+  std::map<std::string, int> index;
+  for (size_t i = 0; i < lora_targets_.size(); ++i) index[lora_targets_[i].name] = (int)i;
+  std::vector<int> named(lora_targets_.size(), -1);
+  size_t stage_floats = 0;
+  for (int i = 0; i < n_pairs; ++i) {
+    const anyref_lora_pair& p = pairs[i];
+    if (!p.weight_name) throw std::runtime_error("anyref_adapter_apply: pair " + std::to_string(i) + " has no weight_name");
+    const std::string name = p.weight_name;
+    auto it = index.find(name);
+    if (it == index.end()) throw std::runtime_error(name + " is not a reserved LoRA target of this handle");
+    if (p.r < 1 || p.r > 64) throw std::runtime_error(name + ": LoRA rank " + std::to_string(p.r) + " is outside 1 .. 64");
+    if (!p.A || !p.B) throw std::runtime_error(name + ": null lora_A / lora_B");
+    if (named[it->second] >= 0) throw std::runtime_error(name + " is named twice in one anyref_adapter_apply");
+    named[it->second] = i;
+    const LoraTarget& tg = lora_targets_[it->second];
+    if (!p.is_device || p.transposed) stage_floats += (size_t)p.r * ((size_t)tg.N + tg.K) + 8;
+  }
+  // ---- host / transposed pairs -> f32 [r,K] and [N,r] on the device ----
+  if (stage_floats > lora_stage_cap_) {
+    if (lora_stage_) dfree(lora_stage_);
+    lora_stage_ = talloc<float>(stage_floats);
+    lora_stage_cap_ = stage_floats;
+  }
+  std::vector<LoraJob> jobs;
+  size_t off = 0;
+  for (size_t t = 0; t < lora_targets_.size(); ++t) {
+    const LoraTarget& tg = lora_targets_[t];
+    if (named[t] < 0) {
+      if (tg.r) jobs.push_back(LoraJob{(int)t, nullptr, nullptr, 0});  // held an adapter: back to the base
+      continue;
+    }
+    const anyref_lora_pair& p = pairs[named[t]];
+    LoraJob j{(int)t, p.A, p.B, p.r};
+    if (!p.is_device || p.transposed) {
+      const size_t na = (size_t)p.r * tg.K, nb = (size_t)tg.N * p.r;
+      // transposed: A is [r,N], B is [K,r]; delta[n,k] = sum_j B[k,j] A[j,n], i.e. the pair (A' = B^T [r,K], B' = A^T [N,r])
+      std::vector<float> ha(p.transposed ? nb : na), hb(p.transposed ? na : nb);
+      const hipMemcpyKind kind = p.is_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
+      HIP_TRY(hipMemcpy(ha.data(), p.A, ha.size() * 4, kind));
+      HIP_TRY(hipMemcpy(hb.data(), p.B, hb.size() * 4, kind));
+      if (p.transposed) {
+        std::vector<float> a2(na), b2(nb);
+        for (int jj = 0; jj < p.r; ++jj)
+          for (int k = 0; k < tg.K; ++k) a2[(size_t)jj * tg.K + k] = hb[(size_t)k * p.r + jj];
+        for (int n = 0; n < tg.N; ++n)
+          for (int jj = 0; jj < p.r; ++jj) b2[(size_t)n * p.r + jj] = ha[(size_t)jj * tg.N + n];
+        ha.swap(a2);
+        hb.swap(b2);
+      }
+      float* da = lora_stage_ + off;
+      off += (na + 3) / 4 * 4;
+      float* db = lora_stage_ + off;
+      off += (nb + 3) / 4 * 4;
+      HIP_TRY(hipMemcpy(da, ha.data(), na * 4, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(db, hb.data(), nb * 4, hipMemcpyHostToDevice));
+      j.A = da;
+      j.B = db;
+    }
+    jobs.push_back(j);
+  }
+  // ---- nothing of this handle may be in flight on the side stream; then the writes ----
+  end_session("anyref_adapter_apply");
+  draft_ids_.clear();
+  join_sam(s);
+  HIP_TRY(hipEventRecord(ev_sam_, s2_));
+  HIP_TRY(hipStreamWaitEvent(s, ev_sam_, 0));
+  lora_run(s, jobs, scaling);
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::update_weight(hipStream_t s, const char* name_c, const void* ptr, int is_device, int dtype, const int64_t* shape,
+                                 int ndim) {
+  HIP_TRY(hipSetDevice(device_));
+  if (!finalized_) throw std::runtime_error("anyref_update_weight before anyref_finalize (use anyref_set_weight)");
+  if (lora_targets_.empty())
+    throw std::runtime_error("anyref_update_weight: this handle reserved no adapter targets (anyref_adapter_reserve before "
+                             "anyref_finalize; adapters= in Python)");
+  if (!name_c || !ptr || !shape || ndim < 1 || ndim > 4) throw std::runtime_error("anyref_update_weight: null / bad argument");
+  if (dtype != ANYREF_F32 && dtype != ANYREF_BF16 && dtype != ANYREF_F16) throw std::runtime_error("bad dtype");
+  const std::string name = name_c;
+  const anyref_config& c = cfg;
+  const int H = c.llm_dim, V = c.llm_vocab, C = c.sam_out_chans, nt = c.num_mask_tokens;
+  std::vector<int64_t> got(shape, shape + ndim);
+  int64_t n = 1;
+  for (auto d : got) n *= d;
+  auto want = [&](std::vector<int64_t> w) {
+    if (got == w) return;
+    auto txt = [](const std::vector<int64_t>& v) {
+      std::string t = "[";
+      for (size_t i = 0; i < v.size(); ++i) t += (i ? ", " : "") + std::to_string(v[i]);
+      return t + "]";
+    };
+    throw std::runtime_error("anyref_update_weight: " + name + " has shape " + txt(got) + ", the handle was built with " + txt(w));
+  };
+  // ---- which tensor, and its built shape (checked before anything is written) ----
+  enum Kind { kEmb, kHead, kF32Copy, kAudioW, kConvTW, kConvTB } kind = kF32Copy;
+  float* f32_dst = nullptr;  // kF32Copy / kConvT*
+  int cin = 0, cout = 0;
+  const std::string md = std::string(SAM_P) + "mask_decoder.";
+  if (name == "model.embed_tokens.weight" || name == "lm_head.weight") {
+    if (ndim == 2 && got[0] != V)
+      throw std::runtime_error("anyref_update_weight: " + name + " has " + std::to_string(got[0]) + " rows, the handle was built "
+                               "for a vocabulary of " + std::to_string(V) + " (the vocabulary cannot change after the build)");
+    want({V, H});
+    kind = name[0] == 'l' ? kHead : kEmb;
+  } else if (name == "model.text_hidden_fcs.0.0.weight") { want({H, H}); f32_dst = fc1_.w;
+  } else if (name == "model.text_hidden_fcs.0.0.bias") { want({H}); f32_dst = fc1_.b;
+  } else if (name == "model.text_hidden_fcs.0.2.weight") { want({c.out_dim, H}); f32_dst = fc2_.w;
+  } else if (name == "model.text_hidden_fcs.0.2.bias") { want({c.out_dim}); f32_dst = fc2_.b;
+  } else if (name == "model.audio_projector.weight" || name == "model.audio_projector.bias") {
+    if (!has_audio_) throw std::runtime_error("anyref_update_weight: " + name + ": the handle was built without an audio projector");
+    if (name.back() == 't') { want({H, c.audio_dim}); kind = kAudioW; }
+    else { want({H}); f32_dst = audio_proj_.b; }
+  } else if (name == md + "mask_tokens.weight") { want({nt, C}); f32_dst = out_tokens_ + C;
+  } else if (name == md + "output_upscaling.0.weight") { want({C, C / 4, 2, 2}); kind = kConvTW; f32_dst = up1_.w; cin = C; cout = C / 4;
+  } else if (name == md + "output_upscaling.0.bias") { want({C / 4}); kind = kConvTB; f32_dst = up1_.b; cout = C / 4;
+  } else if (name == md + "output_upscaling.1.weight") { want({C / 4}); f32_dst = up_ln_.g;
+  } else if (name == md + "output_upscaling.1.bias") { want({C / 4}); f32_dst = up_ln_.b;
+  } else if (name == md + "output_upscaling.3.weight") { want({C / 4, C / 8, 2, 2}); kind = kConvTW; f32_dst = up2_.w; cin = C / 4; cout = C / 8;
+  } else if (name == md + "output_upscaling.3.bias") { want({C / 8}); kind = kConvTB; f32_dst = up2_.b; cout = C / 8;
+  } else if (name.compare(0, md.size() + 26, md + "output_hypernetworks_mlps.") == 0) {
+    int t = -1, j = -1;
+    char what[16] = {0};
+    if (sscanf(name.c_str() + md.size() + 26, "%d.layers.%d.%15s", &t, &j, what) != 3 || t < 0 || t >= nt || j < 0 || j > 2 ||
+        (strcmp(what, "weight") && strcmp(what, "bias")))
+      throw std::runtime_error("anyref_update_weight: " + name + " is not a tensor of the hypernetwork MLPs");
+    const int in = hyper_[j].k, out = hyper_[j].n;
+    if (what[0] == 'w') { want({out, in}); f32_dst = hyper_[j].w + (size_t)t * out * in; }
+    else { want({out}); f32_dst = hyper_[j].b + (size_t)t * out; }
+  } else {
+    throw std::runtime_error("anyref_update_weight: " + name + " is not a tensor an adapter saves (embed_tokens, lm_head, "
+                             "text_hidden_fcs, audio_projector, mask_decoder.{mask_tokens, output_upscaling, "
+                             "output_hypernetworks_mlps})");
+  }
+  // ---- an f32 device image of the tensor, as set_weight makes one ----
+  struct Tmp {
+    void* p = nullptr;
+    ~Tmp() { if (p) (void)hipFree(p); }
+  } staged, f32;
+  const size_t esz = dtype == ANYREF_F32 ? 4 : 2;
+  const void* src = ptr;
+  if (!is_device) {
+    HIP_TRY(hipMalloc(&staged.p, (size_t)n * esz));
+    HIP_TRY(hipMemcpyAsync(staged.p, ptr, (size_t)n * esz, hipMemcpyHostToDevice, s));
+    src = staged.p;
+  }
+  const float* img = reinterpret_cast<const float*>(src);
+  if (dtype != ANYREF_F32) {
+    HIP_TRY(hipMalloc(&f32.p, (size_t)n * 4));
+    launch_to_f32(src, dtype, reinterpret_cast<float*>(f32.p), n, s);
+    img = reinterpret_cast<const float*>(f32.p);
+  }
+  end_session("anyref_update_weight");
+  draft_ids_.clear();
+  join_sam(s);
+  HIP_TRY(hipEventRecord(ev_sam_, s2_));
+  HIP_TRY(hipStreamWaitEvent(s, ev_sam_, 0));
+  // ---- repack in place, by the calls finalize makes ----
+  if (kind == kEmb || kind == kHead || kind == kAudioW) {
+    HIP_TRY(hipMemsetAsync(lora_counts_, 0, 2 * sizeof(unsigned long long), s));
+    if (kind == kEmb) launch_convert<W>(img, H, emb_table_, H, V, H, s, lora_counts_);
+    else if (kind == kAudioW) launch_convert<W>(img, c.audio_dim, audio_proj_.w, audio_proj_.stride(), H, c.audio_dim, s, lora_counts_);
+    else if (lm_head_.w8) pack_src_fp8(lm_head_, 0, img, V, H, 1, s, lora_counts_);
+    else launch_convert<W>(img, H, lm_head_.w, lm_head_.stride(), V, H, s, lora_counts_);
+    unsigned long long h[2] = {0, 0};
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(h, lora_counts_, sizeof(h), hipMemcpyDeviceToHost));
+    inexact_ += (int64_t)h[0] - upd_inexact_[name];
+    upd_inexact_[name] = (int64_t)h[0];
+    if (F16W && h[1])
+      throw std::runtime_error(name + ": " + std::to_string(h[1]) + " weight(s) outside the f16 range (|w| > 65504); the handle "
+                               "holds them as inf until the tensor is replaced again");
+  } else if (kind == kConvTW || kind == kConvTB) {
+    std::vector<float> hsrc((size_t)n);
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(hsrc.data(), img, (size_t)n * 4, hipMemcpyDeviceToHost));
+    const std::vector<float> r = kind == kConvTW ? convt_reorder_w(hsrc, cin, cout) : convt_reorder_b(hsrc, cout);
+    HIP_TRY(hipMemcpyAsync(f32_dst, r.data(), r.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  } else {
+    HIP_TRY(hipMemcpyAsync(f32_dst, img, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
 }
 
 template <typename T, typename TS>

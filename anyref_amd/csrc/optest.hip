@@ -534,6 +534,18 @@ int anyref_op_quant_int4(void* stream, const float* src, int N, int K, uint8_t* 
   OP_GUARD(launch_quant_int4_rows(src, K, N, K, q, (K + 127) / 128 * 64, scale_bf16, (K + 127) / 128, (hipStream_t)stream));
 }
 
+int anyref_op_lora_merge(int t, void* stream, const float* base_f32, int d_in, int N, int K, const float* A, const float* B, int r,
+                         float scaling, void* dst, int ld, int row_stride, uint64_t* counts) {
+  OP_GUARD({
+    if (r < 1) throw std::runtime_error("anyref_op_lora_merge: LoRA rank " + std::to_string(r) + " is outside 1 .. 64");
+    auto* c = reinterpret_cast<unsigned long long*>(counts);
+    if (t == 0) launch_lora_merge<float>(base_f32, d_in, N, K, A, B, r, scaling, dst, ld, row_stride, c, (hipStream_t)stream, "anyref_op_lora_merge");
+    else if (t == 1) launch_lora_merge<bf16>(base_f32, d_in, N, K, A, B, r, scaling, dst, ld, row_stride, c, (hipStream_t)stream, "anyref_op_lora_merge");
+    else if (t == 2) launch_lora_merge<f16>(base_f32, d_in, N, K, A, B, r, scaling, dst, ld, row_stride, c, (hipStream_t)stream, "anyref_op_lora_merge");
+    else throw std::runtime_error("anyref_op_lora_merge: t = 0 (f32), 1 (bf16) or 2 (f16)");
+  });
+}
+
 int anyref_op_dequant_int4(void* stream, const uint8_t* q, const void* scale_bf16, int N, int K, void* out_bf16) {
   OP_GUARD(launch_dequant_int4_rows(q, (K + 127) / 128 * 64, scale_bf16, (K + 127) / 128, N, K, out_bf16, K, (hipStream_t)stream));
 }

@@ -69,14 +69,27 @@ _NEEDS_HANDLE = frozenset({
     "generate", "model_forward_new", "forward", "__call__", "encode_images", "sam_encode", "mask_decode", "llm_forward",
     "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
     "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session",
-    "set_rephrase_paths", "early_masks_done"})
+    "set_rephrase_paths", "early_masks_done", "load_adapter", "set_adapter"})
+
+# the tensors an adapter's `modules_to_save` may carry (train.py:375-387) and anyref_update_weight replaces on a live handle
+_SAVED_EXACT = ("model.embed_tokens.weight", "lm_head.weight", "model.text_hidden_fcs.0.0.weight",
+                "model.text_hidden_fcs.0.0.bias", "model.text_hidden_fcs.0.2.weight", "model.text_hidden_fcs.0.2.bias",
+                "model.audio_projector.weight", "model.audio_projector.bias")
+_SAVED_PREFIXES = tuple("model.visual_model.mask_decoder." + p for p in
+                        ("mask_tokens.weight", "output_upscaling.0.", "output_upscaling.1.", "output_upscaling.3.",
+                         "output_hypernetworks_mlps."))
+
+
+def is_replaceable(name: str) -> bool:
+    """whether `set_adapter` can replace this tensor on a built model (anyref_update_weight's list)"""
+    return name in _SAVED_EXACT or name.startswith(_SAVED_PREFIXES)
 
 
 class AnyRefForCausalLM:
     """MI355X-native stand-in for `model.anyref.AnyRefForCausalLM` (inference surface)."""
 
     def __init__(self, cfg: AnyRefConfig, mode: str = "perf", device: int = 0, max_batch: int = 1,
-                 max_seg: int = 4, audio_encoder=None, defer: bool = False, **kwargs):
+                 max_seg: int = 4, audio_encoder=None, defer: bool = False, adapters=None, **kwargs):
         # constructor kwargs of the reference (anyref.py:188-209) that shape the path
         if "seg_token_idx" in kwargs:
             cfg.seg_token_idx = kwargs.pop("seg_token_idx")
@@ -109,6 +122,16 @@ class AnyRefForCausalLM:
         # The reference's success path itself returns 2 values (anyref.py:822), which is what eval_refer_inv.py:135 and
         # eval_coco20i.py:142 unpack: set `model.success_arity = 2` for those scripts.
         self.success_arity = 3
+        # adapter hot-swap: `adapters="qv"` (or projection names) makes the handle keep the unmerged base of
+        # those LLaMA linears so that `load_adapter` / `set_adapter` can switch LoRA checkpoints on the built model; None
+        # (default): nothing is kept and an adapter can only be merged on the host before the build, as ever
+        from .lora import parse_targets
+        self.adapter_targets = parse_targets(adapters)
+        self._adapters: Dict[str, dict] = {}         # load_adapter
+        self.active_adapter: Optional[str] = None
+        self._base_saved: Dict[str, torch.Tensor] = {}   # host copies of the replaceable tensors as built
+        self._saved_active: set = set()              # replaceable tensors that do not hold their built value now
+        self._built_shapes: Dict[str, tuple] = {}
         self._draft_policy: Optional[str] = None     # set_draft_policy
         self._last_answers: Optional[List[List[int]]] = None
         # `from_pretrained` flow: weights are gathered on the host first (base checkpoint, CLIP tower, SAM file,
@@ -127,6 +150,8 @@ class AnyRefForCausalLM:
         if rc != 0:
             raise RuntimeError("anyref_create: " + self.lib.anyref_last_error(None).decode())
         self.h = h
+        if self.adapter_targets:
+            self._check(self.lib.anyref_adapter_reserve(self.h, self.adapter_targets), "adapter_reserve")
 
     @property
     def n_img(self) -> int:
@@ -185,6 +210,9 @@ class AnyRefForCausalLM:
                                                    shape, t.dim()), f"set_weight({name})")
         self._check(self.lib.anyref_finalize(self.h), "finalize")
         self._finalized = True
+        if self.adapter_targets:                 # what an adapter without these tensors, or set_adapter(None), restores
+            self._built_shapes = {k: tuple(v.shape) for k, v in sd.items()}
+            self._base_saved = {k: v.detach().to("cpu", copy=True) for k, v in sd.items() if is_replaceable(k)}
         return [], []
 
     @classmethod
@@ -202,7 +230,7 @@ class AnyRefForCausalLM:
     # ---- construction path of the reference's callers (eval_referseg.py:62-88) --------------
     @classmethod
     def from_pretrained(cls, model_version: str, torch_dtype=None, mode: Optional[str] = None, device: int = 0,
-                        max_batch: int = 1, max_seg: int = 4, max_seq: int = 1024, **model_args):
+                        max_batch: int = 1, max_seg: int = 4, max_seq: int = 1024, adapters=None, **model_args):
         """`AnyRefForCausalLM.from_pretrained(model_version, torch_dtype=..., **model_args)` (eval_referseg.py:70-72)
         on an HF `save_pretrained` directory (sharded safetensors / bin): config.json -> LLM shape, every tensor ->
         host state dict under the reference's names.  `model_args` are the reference constructor's kwargs
@@ -214,7 +242,9 @@ class AnyRefForCausalLM:
         bytes and rate as perf) holds such weights bit for bit, where perf rounds them to bf16 (`inexact_weights` counts
         the elements that changed).  An fp16 checkpoint that has to meet the tolerance bar (identical greedy ids, mask logits
         within 1e-3 of the fp32 forward on the checkpoint's own values) takes `mode="parity16_f16"`: the same exact f16
-        storage, every GEMM operand f32 carried as a pair of f16 terms; `parity16` would round such weights to bf16."""
+        storage, every GEMM operand f32 carried as a pair of f16 terms; `parity16` would round such weights to bf16.
+        `adapters="qv"` (or a list of projection names) makes the built handle keep the unmerged base of those LLaMA linears, so
+        that LoRA checkpoints can be switched on it afterwards (`load_adapter` / `set_adapter`); default None."""
         import json
         import os
         from .checkpoint import read_hf_dir, llm_config_from_hf
@@ -226,7 +256,8 @@ class AnyRefForCausalLM:
         model_args.pop("train_mask_decoder", None)
         if "mm_vision_tower" in hf:
             model_args.setdefault("vision_tower", hf["mm_vision_tower"])
-        m = cls(cfg, mode=mode or "perf", device=device, max_batch=max_batch, max_seg=max_seg, defer=True, **model_args)
+        m = cls(cfg, mode=mode or "perf", device=device, max_batch=max_batch, max_seg=max_seg, defer=True, adapters=adapters,
+                **model_args)
         m._host_sd.update(read_hf_dir(model_version))
         # a merged checkpoint (merge_lora.py:62 `save_pretrained`) already carries the towers: size them from it
         if "train_mask_decoder" in hf and m.vision_pretrained:
@@ -310,8 +341,100 @@ class AnyRefForCausalLM:
         if self._host_sd is None:
             raise RuntimeError("the LoRA merge happens on the host state dict: call it before .cuda() / first use")
         from .checkpoint import merge_lora
-        self.adapter_stats = merge_lora(self._host_sd, adapter_dir)
+        self.adapter_stats = _HostMergeStats(merge_lora(self._host_sd, adapter_dir), self)
         return self
+
+    # ---- adapter hot-swap on the built model (anyref_adapter_apply / anyref_update_weight) ----
+    def load_adapter(self, adapter_dir: str, name: Optional[str] = None) -> str:
+        """Parse a peft adapter directory (`checkpoint.read_adapter`), check it against the built shapes and keep it ready:
+        lora_A / lora_B as f32 on the device (16 MB per adapter at 7B, rank 8), the `modules_to_save` tensors in pinned host
+        memory.  Returns the name `set_adapter` takes (default: the directory's base name).  Needs `adapters=` at
+        construction; weights change only at `set_adapter`."""
+        if not self.adapter_targets:
+            raise RuntimeError("load_adapter: this model keeps no unmerged base to switch adapters on: construct it with "
+                               'adapters="qv" (or the projection names), or merge on the host before .cuda()')
+        from .checkpoint import read_adapter
+        pairs, saved, scaling, fifo = read_adapter(adapter_dir, base_names=self._built_shapes)
+        name = name or os.path.basename(os.path.normpath(adapter_dir))
+        return self.add_adapter(name, pairs, saved, scaling, fifo)
+
+    def add_adapter(self, name: str, pairs, saved, scaling: float, fan_in_fan_out: bool = False) -> str:
+        """`load_adapter` for an adapter already in memory, in `checkpoint.read_adapter`'s terms: `pairs` maps module names
+        (`model.layers.0.self_attn.q_proj`) to `(lora_A, lora_B)`, `saved` reference names to `modules_to_save` tensors."""
+        if not self.adapter_targets:
+            raise RuntimeError('add_adapter: construct the model with adapters="qv" (or the projection names)')
+        self._ensure_built()
+        from .checkpoint import check_adapter_shapes
+        from .lora import device_pair, target_bit, MAX_RANK
+        check_adapter_shapes(pairs, saved, self._built_shapes, fan_in_fan_out)
+        for mod, (a, _b) in pairs.items():
+            if not target_bit(mod + ".weight") & self.adapter_targets:
+                raise ValueError(f"adapter targets {mod}.weight, which this model did not reserve (adapters= names "
+                                 f"{[k for k, v in _lora_bits().items() if v & self.adapter_targets]})")
+            if not 1 <= a.shape[0] <= MAX_RANK:
+                raise ValueError(f"{mod}: LoRA rank {a.shape[0]} is outside 1 .. {MAX_RANK}")
+        for k in saved:
+            if not is_replaceable(k):
+                raise ValueError(f"adapter saves {k}, which cannot be replaced on a built model (merge it on the host instead)")
+        dev = {}
+        for mod, (a, b) in pairs.items():
+            da, db = device_pair(a, b, fan_in_fan_out)
+            dev[mod + ".weight"] = (da.to(self.device), db.to(self.device))
+        pinned = {}
+        for k, v in saved.items():
+            v = v.detach()
+            if v.dtype not in _DT:
+                v = v.float()
+            v = v.contiguous()
+            pinned[k] = v if v.is_cuda else v.pin_memory()
+        self._adapters[name] = dict(pairs=dev, saved=pinned, scaling=float(scaling))
+        return name
+
+    def _update_weight(self, k: str, t: torch.Tensor):
+        if t.dtype not in _DT:
+            t = t.float()
+        t = t.contiguous()
+        shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
+        self._check(self.lib.anyref_update_weight(self.h, self._stream(), k.encode(), _ptr(t), int(t.is_cuda), _DT[t.dtype],
+                                                  shape, t.dim()), f"update_weight({k})")
+
+    def set_adapter(self, name: Optional[str]):
+        """Switch the built model to a loaded adapter, or back to the base model with None: every reserved LoRA target becomes
+        base + scaling * B A by the rule of `anyref_amd/lora.py` (or its base), the adapter's `modules_to_save` tensors replace
+        the built ones and those it does not carry return to their built values.  In place: no rebuild, captured decode
+        graphs stay valid.  Ends an open image session, drops a pending draft and forgets the "last" draft memory."""
+        if not self.adapter_targets:
+            raise RuntimeError('set_adapter: construct the model with adapters="qv" (or the projection names)')
+        if name is not None and name not in self._adapters:
+            raise KeyError(f"no adapter {name!r} loaded (load_adapter first; loaded: {sorted(self._adapters)})")
+        ad = self._adapters[name] if name is not None else dict(pairs={}, saved={}, scaling=1.0)
+        keep = []                                    # the name bytes must outlive the call
+        arr = (_lib.LoraPair * max(len(ad["pairs"]), 1))()
+        for i, (wname, (a, b)) in enumerate(ad["pairs"].items()):
+            keep.append(wname.encode())
+            arr[i].weight_name, arr[i].A, arr[i].B = keep[-1], a.data_ptr(), b.data_ptr()
+            arr[i].r, arr[i].is_device, arr[i].transposed = int(a.shape[0]), 1, 0
+        self._last_answers = None
+        # (an ImageSession this model handed out is ended by the library: its next use raises "session lost: ended by
+        #  anyref_adapter_apply")
+        self._check(self.lib.anyref_adapter_apply(self.h, self._stream(), arr, len(ad["pairs"]), float(ad["scaling"])),
+                    "adapter_apply")
+        self.active_adapter = name
+        for k, v in ad["saved"].items():
+            self._update_weight(k, v)
+        for k in sorted(self._saved_active - set(ad["saved"])):
+            self._update_weight(k, self._base_saved[k])
+        self._saved_active = set(ad["saved"])
+        return self
+
+    def adapter_stats(self) -> dict:
+        """dict(targets_reserved, pairs_active, inexact, last_apply_ms, active_adapter) of `anyref_adapter_stats`:
+        `last_apply_ms` is the device time of the last switch's merge launches."""
+        self._ensure_built()
+        tr, pa, ix, ms = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_double(0.0)
+        self._check(self.lib.anyref_adapter_stats(self.h, C.byref(tr), C.byref(pa), C.byref(ix), C.byref(ms)), "adapter_stats")
+        return dict(targets_reserved=int(tr.value), pairs_active=int(pa.value), inexact=int(ix.value),
+                    last_apply_ms=float(ms.value), active_adapter=self.active_adapter)
 
     def host_state_dict(self):
         """The gathered weights before the build (deferred construction only)."""
@@ -898,6 +1021,23 @@ class AnyRefForCausalLM:
 def _flat_ints(v):
     """ints of a scalar / list / tuple / tensor, flattened (a one-element list as `generate` takes it, or the bare value)"""
     return [int(x) for x in torch.as_tensor(v).reshape(-1).tolist()]
+
+
+class _HostMergeStats(dict):
+    """`model.adapter_stats` after a host-side `merge_adapter`: the merge's counts as a dict, as before adapter hot-swap; calling
+    it gives the live handle's `adapter_stats()` like on any other model."""
+
+    def __init__(self, counts, model):
+        super().__init__(counts)
+        self._model = model
+
+    def __call__(self):
+        return AnyRefForCausalLM.adapter_stats(self._model)
+
+
+def _lora_bits():
+    from .lora import TARGET_BITS
+    return TARGET_BITS
 
 
 class ImageSession:

@@ -8,6 +8,10 @@
 two lines are served here by merging the adapter into the host-side state dict before the handle is built
 (`anyref_amd.checkpoint.merge_lora`: W += (lora_alpha / r) * B @ A on `q_proj` / `v_proj`, `modules_to_save`
 overrides -- `train.py:371-396`).  A caller switches with one import:  `from anyref_amd.peft_compat import PeftModel`.
+
+On a model that is already built AND reserved its LoRA targets (`adapters="qv"`), the same two lines switch the live handle to
+the adapter instead (`load_adapter` + `set_adapter`: the checkpoint sweep of eval_reason.py:188-201 with the model built once).
+A built model without a reservation keeps refusing ("before .cuda").
 """
 from __future__ import annotations
 
@@ -22,8 +26,12 @@ class PeftModel:
         return cls(model, model_id)
 
     def merge_and_unload(self):
-        self.base_model.merge_adapter(self.adapter_dir)
-        return self.base_model
+        m = self.base_model
+        if getattr(m, "h", None) is not None and getattr(m, "adapter_targets", 0):
+            m.set_adapter(m.load_adapter(self.adapter_dir))
+        else:
+            m.merge_adapter(self.adapter_dir)
+        return m
 
     def __getattr__(self, name):            # `.eval()`, `.generate(...)` straight on the un-merged wrapper
         return getattr(self.base_model, name)

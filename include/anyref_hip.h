@@ -331,6 +331,67 @@ int anyref_session_generate(anyref_handle* h, void* stream, const int64_t* suffi
 /* Forget the session (anyref_destroy does the same).  No error if none is open. */
 int anyref_session_close(anyref_handle* h);
 
+/*
+ * Adapter hot-swap: the reference's evaluations load a LoRA adapter each (`lora_name`), and a training run is
+ * evaluated by sweeping its checkpoints (eval_reason.py:188-201).  A handle that RESERVED its LoRA targets before anyref_finalize
+ * keeps their unmerged base and can be switched between adapters, and back to the base, any number of times without drift and
+ * without a rebuild.  A handle that reserves nothing is unchanged in every respect (bytes, arithmetic, entry points).
+ *
+ * The merge rule, for a target with base w [N,K] (handed to anyref_set_weight in dtype d_in), A [r,K], B [N,r] and `scaling`
+ * (= lora_alpha / r, passed as f32):
+ *     acc = 0 (f64);  for j = 0 .. r-1 in this order:  acc = acc + f64(B[n,j]) * f64(A[j,k])    (f32 x f32 is exact in f64)
+ *     m   = f32( acc * f64(scaling) + f64(w[n,k]) )     one f64 multiply, one f64 add, one RNE to f32
+ *     m   = f32( d_in(m) )                              RNE to the dtype the base came in (identity for f32)
+ *     stored = what anyref_finalize makes of an f32 tensor holding m (RNE to the mode's weight type; in PERF_FP8W / PERF_INT4W the
+ *              row / group quantiser runs on the f32 rows of m)
+ * anyref_amd/lora.py states it in torch; the device reproduces it bit for bit.  A target no pair names holds the base exactly as
+ * anyref_finalize converted it.
+ */
+#define ANYREF_LORA_Q 1u
+#define ANYREF_LORA_K 2u
+#define ANYREF_LORA_V 4u
+#define ANYREF_LORA_O 8u
+#define ANYREF_LORA_GATE 16u
+#define ANYREF_LORA_UP 32u
+#define ANYREF_LORA_DOWN 64u
+#define ANYREF_LORA_ALL 127u
+/* Before anyref_finalize (an error after it): `targets` is a mask of ANYREF_LORA_* over the seven linears of every LLaMA layer
+ * (Q | V is the reference's set, train.py:371-374).  anyref_finalize then keeps the raw f32 tensors of those linears instead of
+ * freeing them (no copy; anyref_device_bytes counts them: 4 N K bytes per target, 4.3 GB for Q | V at 7B). */
+int anyref_adapter_reserve(anyref_handle* h, uint32_t targets);
+typedef struct anyref_lora_pair {
+  const char* weight_name; /* the target's state_dict name, e.g. "model.layers.0.self_attn.q_proj.weight" */
+  const float* A;          /* f32 [r,K]  (transposed: [r,N]) */
+  const float* B;          /* f32 [N,r]  (transposed: [K,r]) */
+  int32_t r;               /* 1 .. 64 */
+  int32_t is_device;       /* A and B are device (1) or host (0) memory */
+  int32_t transposed;      /* fan_in_fan_out adapters: delta = (B A)^T, as merge_lora transposes */
+} anyref_lora_pair;
+/* After anyref_finalize on a reserving handle.  SETS the reserved targets, it does not accumulate: every reserved target named in
+ * `pairs` becomes base + scaling * B A by the rule above, every reserved target not named returns to its base; n_pairs = 0
+ * restores the base model.  Everything is validated before anything is written (target reserved, rank 1 .. 64, no name twice,
+ * non-null tensors, finite scaling; A and B must have the shapes stated above): a refused call leaves the weights, an open
+ * session and a pending draft as they were.  The call then waits for the side stream (no co-running SAM encoder or early mask in
+ * flight), writes the packed weight buffers IN PLACE on `stream` (no buffer moves: a captured decode graph replays the new
+ * weights), ends an open image session ("session lost: ended by anyref_adapter_apply"), drops a pending anyref_set_draft and
+ * returns when the writes have completed.  In the f16 modes a merged element past +-65504 fails the call naming the tensor; the
+ * reserved targets are then all back at their base. */
+int anyref_adapter_apply(anyref_handle* h, void* stream, const anyref_lora_pair* pairs, int n_pairs, float scaling);
+/* After anyref_finalize on a reserving handle: replace one of the tensors an adapter's `modules_to_save` carries
+ * (train.py:375-387), repacked into its existing buffer by the code anyref_finalize uses:
+ *   model.embed_tokens.weight, lm_head.weight, model.text_hidden_fcs.0.{0,2}.{weight,bias}, model.audio_projector.{weight,bias},
+ *   and under model.visual_model.mask_decoder.: mask_tokens.weight, output_upscaling.{0,1,3}.{weight,bias},
+ *   output_hypernetworks_mlps.<t>.layers.<j>.{weight,bias}.
+ * Arguments as anyref_set_weight.  The shape must equal the built one (a vocabulary that differs is an error naming both sizes);
+ * any other name is refused.  Same session / draft consequences as anyref_adapter_apply ("ended by anyref_update_weight"). */
+int anyref_update_weight(anyref_handle* h, void* stream, const char* name, const void* ptr, int is_device, int dtype,
+                         const int64_t* shape, int ndim);
+/* targets_reserved: reserved tensors (targets x layers); pairs_active: targets holding a merged adapter now; inexact: as
+ * anyref_inexact_weights for the weights held now; last_apply_ms: device time of the last anyref_adapter_apply's merge launches
+ * (a hipEvent pair around them).  Any pointer may be NULL. */
+int anyref_adapter_stats(anyref_handle* h, int32_t* targets_reserved, int32_t* pairs_active, int64_t* inexact,
+                         double* last_apply_ms);
+
 /* hipGraph replay of the greedy decode step (default 1): one step is ~170 launches with fixed
  * arguments (position / next token live on the device), captured once per batch size.  0 launches
  * them eagerly; the per-kernel profiler below always runs eagerly. */

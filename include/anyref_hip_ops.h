@@ -104,6 +104,13 @@ int anyref_op_gemv_fp8(void* stream, const float* x, const float* gain, float ep
 /* int4 group quantisation used by ANYREF_MODE_PERF_INT4W: src f32 [N,K] (K % 16 == 0) -> nibble rows q u8 [N, ceil(K/128) * 64]
  * (the order of the nibbles inside a 16-byte block is the library's) and scales bf16 [N, ceil(K/128)] */
 int anyref_op_quant_int4(void* stream, const float* src, int N, int K, uint8_t* q, void* scale_bf16);
+/* The LoRA merge of anyref_adapter_apply (lora_merge_rows_kernel; the rule: include/anyref_hip.h, anyref_amd/lora.py) on caller
+ * buffers: base_f32 f32 [N,K] dev (values exactly representable in dtype d_in = ANYREF_F32 / BF16 / F16), A f32 [r,K], B f32 [N,r]
+ * dev, r in 1 .. 64 -> dst of type t (0 f32, 1 bf16, 2 f16): row n at dst + n * row_stride * ld elements (ld >= K; row_stride 1 or
+ * 2), columns [0, K) only.  counts u64 [2] dev or NULL (16-bit t): [0] += elements stored inexactly, [1] += finite values stored
+ * as inf.  t = 0 followed by anyref_op_quant_fp8 / anyref_op_quant_int4 is the quantised modes' path. */
+int anyref_op_lora_merge(int t, void* stream, const float* base_f32, int d_in, int N, int K, const float* A, const float* B,
+                         int r, float scaling, void* dst, int ld, int row_stride, uint64_t* counts);
 /* q, scale as written by anyref_op_quant_int4 -> out bf16 [N,K] = q * scale (exact) */
 int anyref_op_dequant_int4(void* stream, const uint8_t* q, const void* scale_bf16, int N, int K, void* out_bf16);
 /* bf16 GEMM with an int4 weight operand (q, scale as written by anyref_op_quant_int4; K % 64 == 0, anything else is an error):
