@@ -107,6 +107,12 @@ SYMBOLS = {
     "anyref_session_open": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
     "anyref_session_generate": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
     "anyref_session_close": (_I, [_P]),
+    "anyref_session_pool_reserve": (_I, [_P, _I, _I]),
+    "anyref_session_store": (_I, [_P, _P, _I]),
+    "anyref_session_generate_pooled": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
+    "anyref_session_slot_close": (_I, [_P, _I]),
+    "anyref_session_pool_stats": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_L), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "anyref_adapter_reserve": (_I, [_P, C.c_uint32]),
     "anyref_adapter_apply": (_I, [_P, _P, _P, _I, _F]),
     "anyref_update_weight": (_I, [_P, _P, C.c_char_p, _P, _I, _I, C.POINTER(_L), _I]),
@@ -165,6 +171,7 @@ SYMBOLS = {
     "anyref_op_argmax": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_draft_accept": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_kv_broadcast": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "anyref_op_kv_gather": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I]),
     "anyref_op_norm": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _F, _I]),
     "anyref_op_attention": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _I, _I]),
     "anyref_op_attention_tab": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _I, _I]),

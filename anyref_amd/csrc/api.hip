@@ -66,7 +66,7 @@ int anyref_set_weight(anyref_handle* h, const char* name, const void* ptr, int i
   GUARD(h, h->m->set_weight(name, ptr, is_device, dtype, shape, ndim));
 }
 
-int anyref_finalize(anyref_handle* h) { GUARD(h, h->m->end_session("anyref_finalize"); h->m->finalize()); }
+int anyref_finalize(anyref_handle* h) { GUARD(h, h->m->end_session("anyref_finalize"); h->m->end_slots("anyref_finalize"); h->m->finalize()); }
 
 int anyref_generate(anyref_handle* h, void* stream, const float* clip_images, const float* sam_images,
                     const int64_t* input_ids, const int32_t* lens, int B, int Lmax, const float* extra_embeds,
@@ -130,6 +130,29 @@ int anyref_session_generate(anyref_handle* h, void* stream, const int64_t* suffi
 }
 
 int anyref_session_close(anyref_handle* h) { GUARD(h, h->m->session_close()); }
+
+int anyref_session_pool_reserve(anyref_handle* h, int n_slots, int max_prefix_rows) {
+  GUARD(h, h->m->session_pool_reserve(n_slots, max_prefix_rows));
+}
+
+int anyref_session_store(anyref_handle* h, void* stream, int slot) { GUARD(h, h->m->session_store((hipStream_t)stream, slot)); }
+
+int anyref_session_generate_pooled(anyref_handle* h, void* stream, const int32_t* slots, const int64_t* suffix_ids,
+                                   const int32_t* lens, int Q, int Lmax, const float* extra_embeds, const int32_t* extra_slots,
+                                   int n_extra, int max_new_tokens, int eos_token_id, int64_t* out_ids, int32_t* out_lens,
+                                   int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
+                                   float* out_low, float* out_hidden) {
+  GUARD(h, h->m->session_generate_pooled((hipStream_t)stream, slots, suffix_ids, lens, Q, Lmax, extra_embeds, extra_slots, n_extra,
+                                         max_new_tokens, eos_token_id, out_ids, out_lens, out_nseg, out_masks, out_masks_cap,
+                                         mask_offsets, out_low, out_hidden));
+}
+
+int anyref_session_slot_close(anyref_handle* h, int slot) { GUARD(h, h->m->session_slot_close(slot)); }
+
+int anyref_session_pool_stats(anyref_handle* h, int32_t* slots, int32_t* in_use, int64_t* bytes, int32_t* rows_gathered,
+                              int32_t* rows_skipped, double* last_gather_ms) {
+  GUARD(h, h->m->session_pool_stats(slots, in_use, bytes, rows_gathered, rows_skipped, last_gather_ms));
+}
 
 int anyref_set_draft(anyref_handle* h, const int64_t* draft_ids, const int32_t* draft_lens, int B, int Kmax) {
   GUARD(h, h->m->set_draft(draft_ids, draft_lens, B, Kmax));

@@ -410,6 +410,20 @@ void launch_embed_rows(const int64_t* ids, int B, const void* table, int dtype, 
 // P == 0 or r1 <= r0: nothing is launched.  Throws if P > maxS, r0 < 1 or r1 > rows.
 void launch_kv_broadcast(void* base0, int planes0, void* base1, int planes1, int64_t plane_stride, int rows, int maxS,
                          int64_t row_bytes, int P, int r0, int r1, hipStream_t s);
+// Per-row gather / pack of a session pool: the per-row form of the broadcast above.  The working side is a
+// [planes][rows][maxS][row_bytes] buffer behind two bases as there (the K and the V cache of every layer); the pool is
+// [n_slots][planes][maxP][row_bytes], compact.  Item i moves bytes [0, P * row_bytes) of every plane between slot `slot` of the
+// pool and row `row` of the working side: pool -> row (gather), or row -> pool with pack.  One launch covers every plane and up to
+// kKvGatherRows items (more items: further launches); items with P == 0 or skip != 0 are checked and then cost nothing.  16-byte
+// pieces, four in flight per thread, when row_bytes, the strides and the bases allow, 2-byte pieces otherwise; no atomics, no
+// communication between workgroups.  Throws, before anything is launched, if a slot or a row is out of range, P > maxP or
+// P > maxS, or two moved items share a destination (the same row in a gather, the same slot in a pack).
+struct KvGatherItem {
+  int slot, P, row, skip;
+};
+constexpr int kKvGatherRows = 16;
+void launch_kv_gather(void* base0, int planes0, void* base1, int planes1, int64_t plane_stride, int rows, int maxS, void* pool,
+                      int n_slots, int maxP, int64_t row_bytes, const KvGatherItem* items, int n, bool pack, hipStream_t s);
 // row_map[b] = b*maxS + pos[b]; kvlen[b] = pos[b] + 1
 void launch_decode_index(const int* pos, int B, int maxS, int* row_map, int* kvlen, hipStream_t s);
 // tokens[i, 0:n_out] = out_tokens; tokens[i, n_out] = pred[i]   (mask_decoder.py:127-141)

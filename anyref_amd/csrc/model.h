@@ -67,7 +67,49 @@ class ModelBase {
   void end_session(const char* by) {
     if (sess_live_) sess_lost_by_ = by;
     sess_live_ = false;
+    forget_rows();
   }
+  // ---- session pool (anyref_session_pool_* / _store / _generate_pooled) ----
+  virtual void session_pool_reserve(int n_slots, int max_prefix_rows) = 0;
+  virtual void session_store(hipStream_t s, int slot) = 0;
+  virtual void session_generate_pooled(hipStream_t s, const int32_t* slots, const int64_t* suffix_ids, const int32_t* lens, int Q,
+                                       int Lmax, const float* extra_embeds, const int32_t* extra_slots, int n_extra,
+                                       int max_new_tokens, int eos_token_id, int64_t* out_ids, int32_t* out_lens,
+                                       int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
+                                       float* out_low, float* out_hidden) = 0;
+  void session_slot_close(int slot) {
+    if (slot < 0 || slot >= (int)pool_.size()) throw std::runtime_error("session_slot_close: slot outside the pool");
+    pool_[slot] = PoolSlot();
+  }
+  void session_pool_stats(int32_t* slots, int32_t* in_use, int64_t* bytes, int32_t* gathered, int32_t* skipped, double* gather_ms);
+  // what one slot holds on the host; the device part sits at the slot's index in pool_kv_ / pool_hid_ / pool_emb_
+  struct PoolSlot {
+    bool used = false;
+    const char* lost_by = nullptr;  // entry that ended it (for the error text); a store or a close clears it
+    int P = 0;
+    int64_t gen = 0;                // stamped by every store: a cache row holds a slot's prefix only under the same generation
+    std::vector<int64_t> prefix;
+    int32_t rhw[2] = {0, 0}, ohw[2] = {0, 0};
+  };
+  // the entries that change the weights (anyref_adapter_apply, anyref_update_weight, anyref_finalize) end every slot
+  void end_slots(const char* by) {
+    for (auto& sl : pool_)
+      if (sl.used) {
+        sl = PoolSlot();
+        sl.lost_by = by;
+      }
+  }
+  // which (slot, generation) cache row b and image-embedding slot b hold (they are written together); every entry that writes
+  // the working buffers forgets
+  void forget_rows() { row_tag_.assign(row_tag_.size(), {-1, 0}); }
+  std::vector<PoolSlot> pool_;
+  int pool_maxP_ = 0;
+  int64_t pool_gen_ = 0, pool_bytes_ = 0;
+  void *pool_kv_ = nullptr, *pool_hid_ = nullptr, *pool_emb_ = nullptr;
+  std::vector<std::pair<int, int64_t>> row_tag_;
+  int pool_gathered_ = 0, pool_skipped_ = 0;  // rows of the last pooled call
+  void *pool_ev0_ = nullptr, *pool_ev1_ = nullptr;  // hipEvent_t around the last gather
+  bool pool_timed_ = false;
   // ---- adapter hot-swap (anyref_adapter_*) ----
   // before finalize: the LLaMA linears named by `targets` (ANYREF_LORA_* bits) keep their raw f32 tensor past finalize
   void adapter_reserve(uint32_t targets) {

@@ -30,6 +30,30 @@ ModelBase::~ModelBase() {
   (void)hipDeviceSynchronize();
   for (auto& kv : allocs_) (void)hipFree(kv.first);
   if (wcount_) (void)hipFree(wcount_);
+  if (pool_ev0_) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(pool_ev0_));
+  if (pool_ev1_) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(pool_ev1_));
+}
+
+void ModelBase::session_pool_stats(int32_t* slots, int32_t* in_use, int64_t* bytes, int32_t* gathered, int32_t* skipped,
+                                   double* gather_ms) {
+  int used = 0;
+  for (const auto& sl : pool_) used += sl.used ? 1 : 0;
+  if (slots) *slots = (int32_t)pool_.size();
+  if (in_use) *in_use = used;
+  if (bytes) *bytes = pool_bytes_;
+  if (gathered) *gathered = pool_gathered_;
+  if (skipped) *skipped = pool_skipped_;
+  if (gather_ms) {
+    // device time of the last call's gather launches (between two events on the caller's stream); -1: it launched none
+    *gather_ms = -1.0;
+    if (pool_timed_) {
+      HIP_TRY(hipSetDevice(device_));
+      HIP_TRY(hipEventSynchronize(reinterpret_cast<hipEvent_t>(pool_ev1_)));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(pool_ev0_), reinterpret_cast<hipEvent_t>(pool_ev1_)));
+      *gather_ms = ms;
+    }
+  }
 }
 
 unsigned long long* ModelBase::weight_counts() {
@@ -262,6 +286,19 @@ class Model : public ModelBase {
                         const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
                         int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
                         int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) override;
+  void session_pool_reserve(int n_slots, int max_prefix_rows) override;
+  void session_store(hipStream_t s, int slot) override;
+  void session_generate_pooled(hipStream_t s, const int32_t* slots, const int64_t* suffix_ids, const int32_t* lens, int nq,
+                               int Lmax, const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
+                               int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
+                               int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) override;
+  // both session calls: slots == nullptr is the live session in row 0, else the pool slot of every row
+  void session_core(hipStream_t s, const int32_t* slots, const int64_t* suffix_ids, const int32_t* lens, int nq, int Lmax,
+                    const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens, int eos_token_id,
+                    int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks, int64_t out_masks_cap,
+                    int64_t* mask_offsets, float* out_low, float* out_hidden);
+  // the three buffers a slot keeps, moved by launch_kv_gather: K / V prefix rows, hidden prefix rows, image embedding
+  void pool_move(hipStream_t s, const std::vector<KvGatherItem>& items, bool pack);
   void join_sam_public(hipStream_t s) { join_sam(s); }
   void adapter_apply(hipStream_t s, const anyref_lora_pair* pairs, int n_pairs, float scaling) override;
   void update_weight(hipStream_t s, const char* name, const void* ptr, int is_device, int dtype, const int64_t* shape,
@@ -538,7 +575,7 @@ class Model : public ModelBase {
                 const std::vector<int>& seg_pos, const std::vector<int>& reph_s, const int32_t* resized_hw,
                 const int32_t* orig_hw, int32_t* out_nseg, float* out_masks, int64_t out_masks_cap,
                 int64_t* mask_offsets, float* out_low, const float* attn_given = nullptr, int attn_n = 0,
-                bool one_image = false, bool pair = false);
+                bool one_image = false, bool pair = false, bool emb_ready = false);
   // generate() and session_generate() from "first token" to the end of the greedy loop: the lm_head pass on hidden row
   // slen[b] - 1 of every sequence, then the draft-verified or the plain one-token loop (hipGraph step, EOS / ahead rules).
   // `draft` is the call's (already taken) one-shot draft; fed / per_step: the encoder's CU share (generate only); early: early
@@ -1518,6 +1555,7 @@ void Model<T, TS>::adapter_apply(hipStream_t s, const anyref_lora_pair* pairs, i
   }
   // ---- nothing of this handle may be in flight on the side stream; then the writes ----
   end_session("anyref_adapter_apply");
+  end_slots("anyref_adapter_apply");
   draft_ids_.clear();
   join_sam(s);
   HIP_TRY(hipEventRecord(ev_sam_, s2_));
@@ -1609,6 +1647,7 @@ void Model<T, TS>::update_weight(hipStream_t s, const char* name_c, const void* 
     img = reinterpret_cast<const float*>(f32.p);
   }
   end_session("anyref_update_weight");
+  end_slots("anyref_update_weight");
   draft_ids_.clear();
   join_sam(s);
   HIP_TRY(hipEventRecord(ev_sam_, s2_));
@@ -2486,11 +2525,12 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
                         const std::vector<int>& seg_pos, const std::vector<int>& reph_s, const int32_t* resized_hw,
                         const int32_t* orig_hw, int32_t* out_nseg, float* out_masks, int64_t out_masks_cap,
                         int64_t* mask_offsets, float* out_low, const float* attn_given, int attn_n, bool one_image,
-                        bool pair) {
+                        bool pair, bool emb_ready) {
   // seg_b/seg_pos: (image, row of hidden_all_) of every [SEG]; reph_s: rephrase start row per image
   // attn_given (seg_tail only): caller's head-mean last-layer attention [B, attn_n, attn_n] instead of the K cache
   // one_image (session_generate only): every row is about the image whose embedding sits in slot 0 of sam_emb_ already
   // pair (generate / session_generate with reph_pair()): the rephrase terms by the fused launch pair, not the per-image chain
+  // emb_ready (session_generate_pooled only): slot b of sam_emb_ holds row b's image embedding already (gathered from the pool)
   const anyref_config& c = cfg;
   const int H = c.llm_dim, S = c.llm_max_seq, nseg = (int)seg_b.size();
   // join BEFORE anything below can throw: a refused call must not leave the encoder running on the side stream
@@ -2564,7 +2604,7 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
   }
   gemmf(s, seg_h_, H, fc1_, seg_t_, H, nseg, ACT_RELU);
   gemmf(s, seg_t_, H, fc2_, pred_emb_, c.out_dim, nseg, ACT_NONE);
-  if (!sam_ready && !one_image) sam_encoder(s, sam_images, B, sam_emb_);
+  if (!sam_ready && !one_image && !emb_ready) sam_encoder(s, sam_images, B, sam_emb_);
   const int NK = sam_g_ * sam_g_, C = c.sam_out_chans, L = 4 * sam_g_;
   int row = 0;
   for (int b = 0; b < B; ++b) {
@@ -2869,6 +2909,7 @@ template <typename T, typename TS>
 void Model<T, TS>::session_open(hipStream_t s, const float* clip_image, const float* sam_image, const int64_t* prefix_ids,
                                 int prefix_len, const int32_t* resized_hw, const int32_t* orig_hw) {
   session_close();  // opening replaces the session; a refused open leaves none
+  forget_rows();    // (row 0 and image-embedding slot 0 are about to be rewritten)
   HIP_TRY(hipSetDevice(device_));
   const anyref_config& c = cfg;
   if (!finalized_) throw std::runtime_error("session_open before finalize");
@@ -2907,34 +2948,167 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
                                     int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg,
                                     float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets, float* out_low,
                                     float* out_hidden) {
+  session_core(s, nullptr, suffix_ids, lens, nq, Lmax, extra_embeds, extra_slots, n_extra, max_new_tokens, eos_token_id, out_ids,
+               out_lens, out_nseg, out_masks, out_masks_cap, mask_offsets, out_low, out_hidden);
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::session_generate_pooled(hipStream_t s, const int32_t* slots, const int64_t* suffix_ids, const int32_t* lens,
+                                           int nq, int Lmax, const float* extra_embeds, const int32_t* extra_slots, int n_extra,
+                                           int max_new_tokens, int eos_token_id, int64_t* out_ids, int32_t* out_lens,
+                                           int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
+                                           float* out_low, float* out_hidden) {
+  if (!slots) {
+    draft_ids_.clear();
+    throw std::runtime_error("session_generate_pooled: null argument");
+  }
+  session_core(s, slots, suffix_ids, lens, nq, Lmax, extra_embeds, extra_slots, n_extra, max_new_tokens, eos_token_id, out_ids,
+               out_lens, out_nseg, out_masks, out_masks_cap, mask_offsets, out_low, out_hidden);
+}
+
+// ---------------------------------------------------------------------------------------------
+// session pool (anyref_session_pool_reserve / _store)
+// ---------------------------------------------------------------------------------------------
+template <typename T, typename TS>
+void Model<T, TS>::session_pool_reserve(int n_slots, int max_prefix_rows) {
+  HIP_TRY(hipSetDevice(device_));
+  const anyref_config& c = cfg;
+  if (!finalized_) throw std::runtime_error("session_pool_reserve before finalize");
+  const bool release = n_slots == 0 && max_prefix_rows == 0;
+  if (!release && (n_slots < 1 || max_prefix_rows < 1 || max_prefix_rows > c.llm_max_seq))
+    throw std::runtime_error("session_pool_reserve: n_slots >= 1 and max_prefix_rows in [1, llm_max_seq] (0, 0 frees the pool)");
+  if (!release && n_slots == (int)pool_.size() && max_prefix_rows == pool_maxP_) return;  // the pool as it is
+  if (!release)
+    for (const auto& sl : pool_)
+      if (sl.used) throw std::runtime_error("session_pool_reserve: other sizes only while every slot is empty (anyref_session_slot_close)");
+  // nothing queued on any stream may still read or write the old pool
+  if (pool_kv_) {
+    HIP_TRY(hipDeviceSynchronize());
+    dfree(pool_kv_);
+    dfree(pool_hid_);
+    dfree(pool_emb_);
+  }
+  pool_kv_ = pool_hid_ = pool_emb_ = nullptr;
+  pool_.clear();
+  pool_maxP_ = 0;
+  pool_bytes_ = 0;
+  pool_gathered_ = pool_skipped_ = 0;
+  pool_timed_ = false;
+  row_tag_.clear();
+  if (release) return;
+  const size_t H = c.llm_dim, emb = (size_t)sam_g_ * sam_g_ * c.sam_out_chans * 4;
+  const int64_t before = bytes_;
+  pool_kv_ = dalloc((size_t)n_slots * 2 * c.llm_layers * max_prefix_rows * H * sizeof(Q));
+  pool_hid_ = dalloc((size_t)n_slots * max_prefix_rows * H * 4);
+  pool_emb_ = dalloc((size_t)n_slots * emb);
+  pool_bytes_ = bytes_ - before;
+  pool_.assign(n_slots, PoolSlot());
+  pool_maxP_ = max_prefix_rows;
+  row_tag_.assign(c.max_batch, {-1, 0});
+  if (!pool_ev0_) {
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    pool_ev0_ = e0;
+    HIP_TRY(hipEventCreate(&e1));
+    pool_ev1_ = e1;
+  }
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::pool_move(hipStream_t s, const std::vector<KvGatherItem>& kv, bool pack) {
+  const anyref_config& c = cfg;
+  const int S = c.llm_max_seq, H = c.llm_dim, n_slots = (int)pool_.size();
+  constexpr int64_t kv_elem = sizeof(Q);
+  const int64_t emb_bytes = (int64_t)sam_g_ * sam_g_ * c.sam_out_chans * 4;
+  launch_kv_gather(kcache_, c.llm_layers, vcache_, c.llm_layers, (int64_t)cache_layer_stride_ * kv_elem, c.max_batch, S, pool_kv_,
+                   n_slots, pool_maxP_, (int64_t)H * kv_elem, kv.data(), (int)kv.size(), pack, s);
+  launch_kv_gather(hidden_all_, 1, nullptr, 0, (int64_t)c.max_batch * S * H * 4, c.max_batch, S, pool_hid_, n_slots, pool_maxP_,
+                   (int64_t)H * 4, kv.data(), (int)kv.size(), pack, s);
+  // the image embedding: one "position" of sam_g^2 * sam_out_chans floats per slot, for the same (slot, row) pairs
+  std::vector<KvGatherItem> emb(kv);
+  for (auto& it : emb) it.P = 1;
+  launch_kv_gather(sam_emb_, 1, nullptr, 0, (int64_t)c.max_batch * emb_bytes, c.max_batch, 1, pool_emb_, n_slots, 1, emb_bytes,
+                   emb.data(), (int)emb.size(), pack, s);
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::session_store(hipStream_t s, int slot) {
+  HIP_TRY(hipSetDevice(device_));
+  // ---- refusals, before anything is queued ----
+  if (pool_.empty()) throw std::runtime_error("session_store: no pool reserved (anyref_session_pool_reserve)");
+  if (slot < 0 || slot >= (int)pool_.size()) throw std::runtime_error("session_store: slot outside the pool");
+  if (!sess_live_) {
+    if (sess_lost_by_) throw std::runtime_error(std::string("session lost: ended by ") + sess_lost_by_);
+    throw std::runtime_error("no session open (anyref_session_open)");
+  }
+  if (sess_P_ > pool_maxP_) throw std::runtime_error("session_store: the session's prefix has more rows than the pool's max_prefix_rows");
+  pool_move(s, {{slot, sess_P_, 0, 0}}, true);
+  PoolSlot& sl = pool_[slot];
+  sl.used = true;
+  sl.lost_by = nullptr;
+  sl.P = sess_P_;
+  sl.gen = ++pool_gen_;
+  sl.prefix = sess_prefix_;
+  for (int i = 0; i < 2; ++i) {
+    sl.rhw[i] = sess_rhw_[i];
+    sl.ohw[i] = sess_ohw_[i];
+  }
+  // row 0 and image-embedding slot 0 hold exactly what the slot now holds
+  row_tag_[0] = {slot, sl.gen};
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::session_core(hipStream_t s, const int32_t* slots, const int64_t* suffix_ids, const int32_t* lens, int nq,
+                                int Lmax, const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
+                                int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
+                                int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) {
   // the one-shot draft is taken here, as in generate(): whatever happens below, nothing stays armed
   std::vector<std::vector<int64_t>> draft;
   draft.swap(draft_ids_);
   HIP_TRY(hipSetDevice(device_));
   const anyref_config& c = cfg;
+  const bool pooled = slots != nullptr;
+  const std::string who = pooled ? "session_generate_pooled: " : "session_generate: ";
   stat_offered_.assign(nq > 0 ? nq : 0, 0);
   stat_accepted_.assign(nq > 0 ? nq : 0, 0);
   stat_steps_ = stat_passes_ = 0;
   // ---- everything that can refuse the call, before anything is queued ----
-  if (!sess_live_) {
+  if (!pooled && !sess_live_) {
     if (sess_lost_by_) throw std::runtime_error(std::string("session lost: ended by ") + sess_lost_by_);
     throw std::runtime_error("no session open (anyref_session_open)");
   }
-  if (nq < 1 || nq > c.max_batch) throw std::runtime_error("session_generate: queries outside [1, max_batch]");
+  if (pooled && pool_.empty()) throw std::runtime_error(who + "no pool reserved (anyref_session_pool_reserve)");
+  if (nq < 1 || nq > c.max_batch) throw std::runtime_error(who + "queries outside [1, max_batch]");
   if (max_new_tokens < 1) throw std::runtime_error("max_new_tokens must be >= 1");
   if (c.rephrase_weight > 0.f && !reph_paths_)  // (served with anyref_set_rephrase_paths on: DESIGN.md §8.9)
-    throw std::runtime_error("session_generate: rephrase_weight > 0 is not served inside a session (rephrasing reads the last "
+    throw std::runtime_error(who + "rephrase_weight > 0 is not served inside a session (rephrasing reads the last "
                              "layer's queries of the whole prompt, which the extend path does not keep)");
-  if (!suffix_ids || !lens || !out_ids || !out_lens || !out_nseg || !mask_offsets) throw std::runtime_error("session_generate: null argument");
+  if (!suffix_ids || !lens || !out_ids || !out_lens || !out_nseg || !mask_offsets) throw std::runtime_error(who + "null argument");
   if (!draft.empty() && (int)draft.size() != nq) throw std::runtime_error("the pending draft was set for another batch size");
-  const int H = c.llm_dim, S = c.llm_max_seq, n_img = clip_n_, P = sess_P_, np = (int)sess_prefix_.size();
-  int n = 0;
+  const int H = c.llm_dim, S = c.llm_max_seq, n_img = clip_n_;
+  // per row: spliced prefix rows, prefix ids, sizes -- the live session's for every row, or the row's slot's
+  std::vector<int> Pb(nq, sess_P_);
+  std::vector<const std::vector<int64_t>*> pre(nq, &sess_prefix_);
+  if (pooled)
+    for (int b = 0; b < nq; ++b) {
+      const int k = slots[b];
+      if (k < 0 || k >= (int)pool_.size()) throw std::runtime_error(who + "slot " + std::to_string(k) + " outside the pool");
+      const PoolSlot& sl = pool_[k];
+      if (!sl.used) {
+        if (sl.lost_by) throw std::runtime_error("slot " + std::to_string(k) + " lost: ended by " + sl.lost_by);
+        throw std::runtime_error(who + "slot " + std::to_string(k) + " is empty (anyref_session_store)");
+      }
+      Pb[b] = sl.P;
+      pre[b] = &sl.prefix;
+    }
+  int n = 0, np = 0;  // np: the longest prefix of the call, in ids
   for (int b = 0; b < nq; ++b) {
-    if (lens[b] < 1 || lens[b] > Lmax) throw std::runtime_error("session_generate: suffix length outside [1, Lmax]");
-    if (P + lens[b] + max_new_tokens > S) throw std::runtime_error("session_generate: prefix + suffix + max_new_tokens exceeds llm_max_seq");
+    if (lens[b] < 1 || lens[b] > Lmax) throw std::runtime_error(who + "suffix length outside [1, Lmax]");
+    if (Pb[b] + lens[b] + max_new_tokens > S) throw std::runtime_error(who + "prefix + suffix + max_new_tokens exceeds llm_max_seq");
     n = std::max(n, lens[b]);
+    np = std::max(np, (int)pre[b]->size());
   }
-  if (n_extra < 0 || (n_extra > 0 && (!extra_embeds || !extra_slots))) throw std::runtime_error("session_generate: bad extra rows");
+  if (n_extra < 0 || (n_extra > 0 && (!extra_embeds || !extra_slots))) throw std::runtime_error(who + "bad extra rows");
   if (n_extra > (int)c.max_batch * std::max(c.max_seg, 64)) throw std::runtime_error("too many extra slots");
   std::vector<char> replaced((size_t)nq * n, 0);
   for (int i = 0; i < n_extra; ++i) {
@@ -2946,12 +3120,12 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
   for (int b = 0; b < nq; ++b)
     for (int i = 0; i < lens[b]; ++i) {
       const int64_t id = suffix_ids[(size_t)b * Lmax + i];
-      if (id == -200) throw std::runtime_error("session_generate: image placeholder inside a suffix");
+      if (id == -200) throw std::runtime_error(who + "image placeholder inside a suffix");
       if (id >= 0 && id < c.llm_vocab) sess_ids_[(size_t)b * n + i] = id;
-      else if (!replaced[(size_t)b * n + i]) throw std::runtime_error("session_generate: a suffix id outside the vocabulary has no extra row");
+      else if (!replaced[(size_t)b * n + i]) throw std::runtime_error(who + "a suffix id outside the vocabulary has no extra row");
     }
-  std::vector<int> slen(nq), pos0(nq, P);
-  for (int b = 0; b < nq; ++b) slen[b] = P + lens[b];
+  std::vector<int> slen(nq), pos0(Pb);
+  for (int b = 0; b < nq; ++b) slen[b] = Pb[b] + lens[b];
   early_done_ = 0;  // see forward_teacher
   early_stop_ = false;
   early_masks_last_ = 0;
@@ -2960,7 +3134,31 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
   const bool pair = reph_pair();
   if (pair) ensure_reph();
   // ---- 1. the prefix for cache rows that do not hold it yet: K, V of every layer in one launch, the hidden rows in another ----
-  if (nq > sess_rows_) {
+  if (pooled) {
+    // every row's prefix from its slot, all layers, K and V, all rows in one launch; the hidden rows and the image embeddings in
+    // two more of the same kernel.  A row that still holds its slot's prefix under the slot's generation is skipped: queries
+    // only write positions >= P.  The call writes row 0: an unpooled live session ends here (the refusals are behind us).
+    if (sess_live_) sess_lost_by_ = "anyref_session_generate_pooled";
+    sess_live_ = false;
+    std::vector<KvGatherItem> items(nq);
+    int moved = 0;
+    for (int b = 0; b < nq; ++b) {
+      const std::pair<int, int64_t> tag{slots[b], pool_[slots[b]].gen};
+      items[b] = {slots[b], Pb[b], b, row_tag_[b] == tag};
+      moved += items[b].skip ? 0 : 1;
+      row_tag_[b] = tag;
+    }
+    pool_gathered_ = moved;
+    pool_skipped_ = nq - moved;
+    pool_timed_ = false;
+    if (moved > 0) {
+      HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(pool_ev0_), s));
+      pool_move(s, items, false);
+      HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(pool_ev1_), s));
+      pool_timed_ = true;
+    }
+  } else if (nq > sess_rows_) {
+    const int P = sess_P_;
     constexpr int64_t kv_elem = sizeof(Q);  // the cache element (the class's type Q: f32 in the parity modes, 16-bit in perf)
     static_assert(kv_elem == sizeof(*kcache_), "the broadcast is sized by the cache element");
     launch_kv_broadcast(kcache_, c.llm_layers, vcache_, c.llm_layers, (int64_t)cache_layer_stride_ * kv_elem, c.max_batch, S,
@@ -2969,6 +3167,7 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
                         nq, s);
     sess_rows_ = nq;
   }
+  if (!pooled) forget_rows();  // (rows [0, nq) now hold the live session's prefix, whatever slot's they held)
   // ---- 2. the suffix rows' embeddings, compact [nq, n, H] ----
   HIP_TRY(hipMemcpyAsync(ids_dev_, sess_ids_.data(), (size_t)nq * n * 8, hipMemcpyHostToDevice, s));
   launch_embed_rows(ids_dev_, nq * n, emb_table_, kEmbDtype, H, l_x_, s);
@@ -3002,16 +3201,19 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
   la.max_new_tokens = max_new_tokens; la.eos_token_id = eos_token_id; la.keep_q = keep_q; la.draft_keeps_q = reph_paths_;
   std::vector<std::vector<int64_t>> gen;
   decode_loop(s, nq, slen, draft, la, gen);
-  // ---- 7. ids and masks: generate()'s arithmetic on prefix + suffix + answer, every row about the one image ----
+  // ---- 7. ids and masks: generate()'s arithmetic on prefix + suffix + answer, every row about its own image (the live
+  // session: the one image).  Rows are np + Lmax + max_new_tokens apart, np the longest prefix of the call
   const int Lout = np + Lmax + max_new_tokens, shift = n_img - 1;
   std::vector<int> seg_b, seg_pos, reph(nq, 0);
   for (int b = 0; b < nq; ++b) {
     int64_t* row = out_ids + (size_t)b * Lout;
+    const std::vector<int64_t>& pf = *pre[b];
+    const int npb = (int)pf.size();
     for (int i = 0; i < Lout; ++i) row[i] = 0;
-    for (int i = 0; i < np; ++i) row[i] = sess_prefix_[i];
-    for (int i = 0; i < lens[b]; ++i) row[np + i] = suffix_ids[(size_t)b * Lmax + i];
-    for (size_t i = 0; i < gen[b].size(); ++i) row[np + lens[b] + i] = gen[b][i];
-    out_lens[b] = np + lens[b] + (int)gen[b].size();
+    for (int i = 0; i < npb; ++i) row[i] = pf[i];
+    for (int i = 0; i < lens[b]; ++i) row[npb + i] = suffix_ids[(size_t)b * Lmax + i];
+    for (size_t i = 0; i < gen[b].size(); ++i) row[npb + lens[b] + i] = gen[b][i];
+    out_lens[b] = npb + lens[b] + (int)gen[b].size();
     for (int p = 0; p + 1 < out_lens[b]; ++p) {  // [SEG] search in output_ids[:,1:], hidden row p + n_img - 1
       const int64_t id = row[p + 1];
       if (id >= c.seg_lo && id <= c.seg_hi) {
@@ -3026,11 +3228,11 @@ void Model<T, TS>::session_generate(hipStream_t s, const int64_t* suffix_ids, co
   sess_hw_.resize((size_t)4 * nq);
   for (int b = 0; b < nq; ++b)
     for (int i = 0; i < 2; ++i) {
-      sess_hw_[2 * b + i] = sess_rhw_[i];
-      sess_hw_[2 * nq + 2 * b + i] = sess_ohw_[i];
+      sess_hw_[2 * b + i] = pooled ? pool_[slots[b]].rhw[i] : sess_rhw_[i];
+      sess_hw_[2 * nq + 2 * b + i] = pooled ? pool_[slots[b]].ohw[i] : sess_ohw_[i];
     }
   run_tail(s, nullptr, nq, seg_b, seg_pos, reph, sess_hw_.data(), sess_hw_.data() + 2 * nq, out_nseg, out_masks, out_masks_cap,
-           mask_offsets, out_low, nullptr, 0, true, pair);
+           mask_offsets, out_low, nullptr, 0, !pooled, pair, pooled);
   if (out_hidden)
     HIP_TRY(hipMemcpyAsync(out_hidden, hidden_all_, (size_t)nq * S * H * 4, hipMemcpyDeviceToDevice, s));
 }

@@ -1027,6 +1027,85 @@ void launch_kv_broadcast(void* base0, int planes0, void* base1, int planes1, int
     hipLaunchKernelGGL(kv_broadcast_kernel<unsigned short>, grid, dim3(256), 0, s, (char*)base0, planes0, (char*)base1,
                        plane_stride, row_stride, nvec, r0, r1);
 }
+// Per-row gather / pack (session pools): the broadcast's loop with a table.  blockIdx.y is the plane, blockIdx.z the table row:
+// byte offsets of the row inside a plane on either side and its number of pieces.  A side is `planes0` planes behind base0 and
+// the rest behind base1, stride bytes apart (the working side: K and V cache; the pool: one buffer, base1 = nullptr).
+struct KvGatherRow {
+  int64_t src_off, dst_off, nvec;
+};
+struct KvGatherTable {
+  KvGatherRow r[kKvGatherRows];
+};
+struct KvSide {
+  char* base0;
+  char* base1;
+  int planes0;
+  int64_t stride;
+  __device__ char* plane(int p) const { return p < planes0 ? base0 + (int64_t)p * stride : base1 + (int64_t)(p - planes0) * stride; }
+};
+template <typename V>
+__global__ void kv_gather_kernel(KvSide src_side, KvSide dst_side, KvGatherTable t) {
+  const int plane = blockIdx.y;
+  const int64_t nvec = t.r[blockIdx.z].nvec;
+  const V* __restrict__ src = reinterpret_cast<const V*>(src_side.plane(plane) + t.r[blockIdx.z].src_off);
+  V* __restrict__ dst = reinterpret_cast<V*>(dst_side.plane(plane) + t.r[blockIdx.z].dst_off);
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + 3 * step < nvec; i += 4 * step) {
+    const V a = src[i], b = src[i + step], c = src[i + 2 * step], d = src[i + 3 * step];
+    dst[i] = a; dst[i + step] = b; dst[i + 2 * step] = c; dst[i + 3 * step] = d;
+  }
+  for (; i < nvec; i += step) dst[i] = src[i];
+}
+void launch_kv_gather(void* base0, int planes0, void* base1, int planes1, int64_t plane_stride, int rows, int maxS, void* pool,
+                      int n_slots, int maxP, int64_t row_bytes, const KvGatherItem* items, int n, bool pack, hipStream_t s) {
+  if (!base0 || planes0 < 1 || planes1 < 0 || (planes1 > 0 && !base1) || rows < 1 || maxS < 1 || row_bytes < 2 || (row_bytes & 1))
+    throw std::runtime_error("kv_gather: bad buffer description");
+  if (!pool || n_slots < 1 || maxP < 1) throw std::runtime_error("kv_gather: bad pool description");
+  if (n < 0 || (n > 0 && !items)) throw std::runtime_error("kv_gather: bad table");
+  const int planes = planes0 + planes1;
+  const int64_t row_stride = (int64_t)maxS * row_bytes, pool_plane = (int64_t)maxP * row_bytes, pool_slot = planes * pool_plane;
+  if (plane_stride < (int64_t)rows * row_stride && planes > 1) throw std::runtime_error("kv_gather: planes overlap");
+  std::vector<KvGatherRow> tab;
+  std::vector<int> dests;
+  int64_t top = 0;
+  bool v16 = row_bytes % 16 == 0 && plane_stride % 16 == 0 && !((reinterpret_cast<uintptr_t>(base0) | reinterpret_cast<uintptr_t>(pool)) & 15) &&
+             (planes1 == 0 || (reinterpret_cast<uintptr_t>(base1) & 15) == 0);
+  for (int i = 0; i < n; ++i) {
+    const KvGatherItem& it = items[i];
+    if (it.slot < 0 || it.slot >= n_slots) throw std::runtime_error("kv_gather: slot outside [0, n_slots)");
+    if (it.row < 0 || it.row >= rows) throw std::runtime_error("kv_gather: row outside [0, rows)");
+    if (it.P < 0 || it.P > maxP || it.P > maxS) throw std::runtime_error("kv_gather: P outside [0, min(max_prefix_rows, maxS)]");
+    if (it.P == 0 || it.skip) continue;
+    const int dest = pack ? it.slot : it.row;
+    for (int d : dests)
+      if (d == dest) throw std::runtime_error(pack ? "kv_gather: two rows packed into one slot" : "kv_gather: two slots gathered into one row");
+    dests.push_back(dest);
+    const int64_t w_off = (int64_t)it.row * row_stride, p_off = (int64_t)it.slot * pool_slot;
+    tab.push_back(pack ? KvGatherRow{w_off, p_off, (int64_t)it.P * row_bytes} : KvGatherRow{p_off, w_off, (int64_t)it.P * row_bytes});
+  }
+  if (tab.empty()) return;
+  const int64_t piece = v16 ? 16 : 2;
+  for (auto& r : tab) {
+    r.nvec /= piece;  // (bytes until here)
+    top = std::max(top, r.nvec);
+  }
+  KvSide work{(char*)base0, (char*)base1, planes0, plane_stride}, pl{(char*)pool, nullptr, planes, pool_plane};
+  for (size_t t0 = 0; t0 < tab.size(); t0 += kKvGatherRows) {
+    const int nt = (int)std::min<size_t>(kKvGatherRows, tab.size() - t0);
+    KvGatherTable t{};
+    for (int i = 0; i < nt; ++i) t.r[i] = tab[t0 + i];
+    // grid sized to the bytes: one thread per four pieces, capped at about 2048 workgroups over all planes and rows (the rest
+    // is the grid-stride loop); a shorter row's surplus workgroups leave at once
+    const int64_t want = (top + 4 * 256 - 1) / (4 * 256);
+    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, std::max(1, 2048 / (planes * nt))));
+    dim3 grid(gx, planes, nt);
+    if (v16)
+      hipLaunchKernelGGL(kv_gather_kernel<uint4>, grid, dim3(256), 0, s, pack ? work : pl, pack ? pl : work, t);
+    else
+      hipLaunchKernelGGL(kv_gather_kernel<unsigned short>, grid, dim3(256), 0, s, pack ? work : pl, pack ? pl : work, t);
+  }
+}
 __global__ void decode_index_kernel(const int* __restrict__ pos, int B, int maxS, int* __restrict__ row_map,
                                     int* __restrict__ kvlen) {
   const int b = threadIdx.x;

@@ -390,6 +390,21 @@ int anyref_op_kv_broadcast(void* stream, void* kc, void* vc, int layers, int row
   });
 }
 
+int anyref_op_kv_gather(void* stream, void* kc, void* vc, int layers, int rows, int maxS, void* pool, int n_slots, int maxP,
+                        int row_elems, int elem_size, const int32_t* table, int n, int pack) {
+  OP_GUARD({
+    if (!kc || !pool || (n > 0 && !table)) throw std::runtime_error("op_kv_gather: null argument");
+    if (elem_size != 2 && elem_size != 4) throw std::runtime_error("op_kv_gather: elem_size 2 / 4");
+    if (layers < 1 || rows < 1 || maxS < 1 || row_elems < 1 || n_slots < 1 || maxP < 1 || n < 0)
+      throw std::runtime_error("op_kv_gather: bad shape");
+    const int64_t row_bytes = (int64_t)row_elems * elem_size;
+    std::vector<KvGatherItem> items(n);
+    for (int i = 0; i < n; ++i) items[i] = KvGatherItem{table[4 * i], table[4 * i + 1], table[4 * i + 2], table[4 * i + 3]};
+    launch_kv_gather(kc, layers, vc, vc ? layers : 0, (int64_t)rows * maxS * row_bytes, rows, maxS, pool, n_slots, maxP, row_bytes,
+                     items.data(), n, pack != 0, (hipStream_t)stream);
+  });
+}
+
 int anyref_op_norm(int t, void* stream, const float* x, const float* gain, const float* bias, float* y, int M,
                    int D, float eps, int rms) {
   OP_GUARD({

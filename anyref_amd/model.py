@@ -68,7 +68,7 @@ def _c_config(cfg: AnyRefConfig, mode: int, max_batch: int, max_seg: int) -> _li
 _NEEDS_HANDLE = frozenset({
     "generate", "model_forward_new", "forward", "__call__", "encode_images", "sam_encode", "mask_decode", "llm_forward",
     "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
-    "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session",
+    "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session", "session_pool",
     "set_rephrase_paths", "early_masks_done", "load_adapter", "set_adapter"})
 
 # the tensors an adapter's `modules_to_save` may carry (train.py:375-387) and anyref_update_weight replaces on a live handle
@@ -134,6 +134,7 @@ class AnyRefForCausalLM:
         self._built_shapes: Dict[str, tuple] = {}
         self._draft_policy: Optional[str] = None     # set_draft_policy
         self._last_answers: Optional[List[List[int]]] = None
+        self._session_pool = None                    # the SessionPool this model handed out last (told when its slots are ended)
         # `from_pretrained` flow: weights are gathered on the host first (base checkpoint, CLIP tower, SAM file,
         # token-row resize, LoRA merge all happen BEFORE `.cuda()` in the callers) and go to HBM in one build
         self._host_sd: Optional[Dict[str, torch.Tensor]] = {} if defer else None
@@ -397,6 +398,12 @@ class AnyRefForCausalLM:
         shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
         self._check(self.lib.anyref_update_weight(self.h, self._stream(), k.encode(), _ptr(t), int(t.is_cuda), _DT[t.dtype],
                                                   shape, t.dim()), f"update_weight({k})")
+        self._slots_ended()
+
+    def _slots_ended(self):
+        """the library ended every slot of the session pool (a weight changed): the Python pool forgets its sessions too"""
+        if self._session_pool is not None:
+            self._session_pool._forget_all()
 
     def set_adapter(self, name: Optional[str]):
         """Switch the built model to a loaded adapter, or back to the base model with None: every reserved LoRA target becomes
@@ -419,6 +426,7 @@ class AnyRefForCausalLM:
         #  anyref_adapter_apply")
         self._check(self.lib.anyref_adapter_apply(self.h, self._stream(), arr, len(ad["pairs"]), float(ad["scaling"])),
                     "adapter_apply")
+        self._slots_ended()
         self.active_adapter = name
         for k, v in ad["saved"].items():
             self._update_weight(k, v)
@@ -936,6 +944,29 @@ class AnyRefForCausalLM:
         the model (`generate`, `forward`, `llm_forward`, `encode_images`, ...) ends it."""
         return ImageSession(self, clip_image, sam_image, sam_resized_size, height, width, prefix_ids)
 
+    def session_pool(self, slots: int, max_prefix_rows: Optional[int] = None) -> "SessionPool":
+        """Keep up to `slots` images resident and ask about any of them, several per call (`anyref_session_pool_reserve`,
+        DESIGN.md §8.11): a stream that interleaves images pays one open per NEW image instead of one per switch, questions about
+        different images share a call, and plain calls in between (`generate`, `forward`, ...) do not lose the images.
+
+            pool = model.session_pool(8)
+            ps = pool.get(image_id) or pool.open(image_id, clip, sam, resized, h, w, ids[: image_pos + 1])
+            out_ids, masks, _ = pool.generate([ps_a, ps_b, ps_a], prompts, max_new_tokens=...)
+
+        A slot reserves `max_prefix_rows` prefix rows of every layer's K and V (default: llm_max_seq - 2, capped at the image rows
+        + 128 prompt ids -- `session.default_max_prefix_rows`); at LLaMA-7B with 16-bit caches about 0.52 MB per row and slot.
+        One pool per model: a second call re-reserves, which the library allows only while every slot is empty, and closes
+        the pool handed out before.  Switching
+        an adapter (`set_adapter`) ends every slot in the library ("slot N lost: ended by ..." at the C entry); the pool then
+        forgets its sessions as well: `pool.get(key)` returns None, a session object handed out before raises on use, and the
+        images are opened again."""
+        pool = SessionPool(self, slots, max_prefix_rows)   # (raises, and changes nothing, if the library refuses to re-reserve)
+        if self._session_pool is not None:           # the pool before it shares the library's slots: it is closed
+            self._session_pool._forget_all()
+            self._session_pool.closed = True
+        self._session_pool = pool
+        return pool
+
     def forward(self, **kwargs):
         """`AnyRefForCausalLM.forward` (anyref.py:233-237): dispatch as the reference does."""
         if "past_key_values" in kwargs:
@@ -1129,6 +1160,206 @@ class ImageSession:
         if _return_extras:
             return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **m.draft_stats(Q))
         return res
+
+
+class PooledSession:
+    """what `SessionPool.open` returns: one image resident in one slot of the pool.  `.slot`, `.key`, `.prefix` (the ids up to
+    and including the image placeholder), `.height` / `.width`."""
+
+    def __init__(self, pool, key, slot, gen, prefix, height, width):
+        self.pool, self.key, self.slot, self.gen, self.prefix = pool, key, slot, gen, prefix
+        self.height, self.width = height, width
+
+    def check(self):
+        """raises if the slot no longer holds this session (closed, evicted by a later `open`, or opened again)"""
+        t = self.pool.table
+        if t.slot_of(self.key) != self.slot or t.gens[self.slot] != self.gen:
+            raise RuntimeError(f"pooled session {self.key!r} is gone from slot {self.slot}: it was closed, evicted as the least "
+                               "recently used, its key was opened again, or a weight change (an adapter switch) ended the "
+                               "pool's slots (pool.get(key) returns the current session or None)")
+
+
+class SessionPool:
+    """`AnyRefForCausalLM.session_pool(slots)`: many images resident at once, queries about different images in one call
+    (`anyref_session_pool_reserve` / `_store` / `_generate_pooled`).  The host rules -- key to slot, least
+    recently used eviction, generations, chunking, row placement -- are anyref_amd/session.py's."""
+
+    def __init__(self, model: "AnyRefForCausalLM", slots: int, max_prefix_rows=None):
+        from .session import SlotTable, default_max_prefix_rows
+        self.model = m = model
+        self.table = SlotTable(slots)
+        self.max_prefix_rows = int(max_prefix_rows) if max_prefix_rows is not None else \
+            default_max_prefix_rows(m.cfg.llm.max_seq, m.n_img)
+        m._check(m.lib.anyref_session_pool_reserve(m.h, self.table.n_slots, self.max_prefix_rows), "session_pool_reserve")
+        self._sessions = {}                       # key -> PooledSession
+        self._held = [None] * m.max_batch         # (slot, generation) the cache rows held after the last pooled call
+        self.closed = False
+
+    def _live(self):
+        if self.closed:
+            raise RuntimeError("this session pool was closed (pool.close()): ask the model for a new one")
+
+    def _forget_all(self):
+        """every session is gone (the library ended the slots, or the pool was closed): keys released, generations bumped, so
+        `get` returns None and a session object handed out before fails its `check`"""
+        for key in self.table.lru_order():
+            self.table.release(key)
+        self._sessions.clear()
+        self._held = [None] * self.model.max_batch
+
+    def open(self, key, clip_image, sam_images, sam_resized_sizes, height, width, prefix_ids) -> PooledSession:
+        """Encode the image (`model.image_session`'s open) and store it in a slot under `key`.  A key already held keeps its
+        slot and is replaced; a full pool evicts the least recently used key, whose session object raises on its next use."""
+        m = self.model
+        self._live()
+        sess = ImageSession(m, clip_image, sam_images, sam_resized_sizes, height, width, prefix_ids)
+        P = len(sess.prefix) + m.n_img - 1
+        if P > self.max_prefix_rows:
+            sess.close()
+            raise ValueError(f"the prefix splices to {P} rows, the pool was reserved for max_prefix_rows = {self.max_prefix_rows}")
+        slot, evicted = self.table.assign(key)
+        self._sessions.pop(evicted, None)
+        try:
+            m._check(m.lib.anyref_session_store(m.h, m._stream(), slot), "session_store")
+        except Exception:
+            self.table.release(key)               # (what the slot held before, if anything, goes with it: both sides agree)
+            self._sessions.pop(key, None)
+            m.lib.anyref_session_slot_close(m.h, slot)
+            raise
+        finally:
+            sess.close()                          # the slot holds it now; the working buffers are free for any other call
+        self._held = [None] * m.max_batch
+        ps = PooledSession(self, key, slot, self.table.gens[slot], sess.prefix, sess.height, sess.width)
+        self._sessions[key] = ps
+        return ps
+
+    def get(self, key):
+        """the session held under `key` (which becomes the most recently used), or None"""
+        self._live()
+        ps = self._sessions.get(key)
+        if ps is not None:
+            self.table.touch(key)
+        return ps
+
+    def close(self, key=None):
+        """close the session held under `key`; without a key: every session, the pool's device memory is released and the
+        pool refuses further use (`model.session_pool(...)` gives a new one)"""
+        m = self.model
+        if key is None:
+            if self.closed:
+                return
+            self._forget_all()
+            self.closed = True
+            if m._session_pool is self:
+                m._session_pool = None
+            if m.h:
+                m._check(m.lib.anyref_session_pool_reserve(m.h, 0, 0), "session_pool_reserve")
+            return
+        self._live()
+        slot = self.table.release(key)
+        self._sessions.pop(key, None)
+        if slot is not None and m.h:
+            m._check(m.lib.anyref_session_slot_close(m.h, slot), "session_slot_close")
+
+    def stats(self) -> dict:
+        """`anyref_session_pool_stats`: slots, in_use, bytes, rows the last pooled call gathered / skipped, its gather's
+        device time in ms (None when it launched none)"""
+        m = self.model
+        i = [C.c_int32() for _ in range(4)]
+        nb, ms = C.c_int64(), C.c_double()
+        m._check(m.lib.anyref_session_pool_stats(m.h, C.byref(i[0]), C.byref(i[1]), C.byref(nb), C.byref(i[2]), C.byref(i[3]),
+                                                 C.byref(ms)), "session_pool_stats")
+        return dict(slots=i[0].value, in_use=i[1].value, bytes=nb.value, rows_gathered=i[2].value, rows_skipped=i[3].value,
+                    gather_ms=None if ms.value < 0 else ms.value)
+
+    @torch.no_grad()
+    def generate(self, sessions, input_ids, audios=None, ref_images=None, max_new_tokens=128, attention_masks=None,
+                 draft_ids=None, _return_extras: bool = False):
+        """`ImageSession.generate` with one session per row: row b of `input_ids` is a question about `sessions[b]`, as a bare
+        suffix or as a full prompt that begins with THAT session's prefix (a row that does not raises ValueError naming the
+        row).  Rows may be about one image or about different images, at most max_batch of them.  Same return shape;
+        `output_ids` rows are the row's own prefix + suffix + answer.  `ref_images` is not served, as in a session."""
+        from .draft import normalize_drafts
+        from .session import cut_rows_each
+        m = self.model
+        self._live()
+        if ref_images is not None:
+            raise NotImplementedError("ref_images inside a pooled session: encode_images needs the working buffers per call")
+        sessions = list(sessions)
+        for ps in sessions:
+            ps.check()
+        ids, lens = m._rows(input_ids, attention_masks)
+        suffixes = cut_rows_each([ids[b, : int(lens[b])].tolist() for b in range(ids.shape[0])], [ps.prefix for ps in sessions])
+        Q, Lmax = len(suffixes), max(len(r) for r in suffixes)
+        if Q > m.max_batch:
+            raise ValueError(f"batch {Q} > max_batch {m.max_batch} the handle was created for")
+        suf = torch.zeros(Q, Lmax, dtype=torch.long)
+        for b, r in enumerate(suffixes):
+            suf[b, : len(r)] = torch.tensor(r, dtype=torch.long)
+        slens = torch.tensor([len(r) for r in suffixes], dtype=torch.int32)
+        slots = torch.tensor([ps.slot for ps in sessions], dtype=torch.int32)
+        extra, eslots, n_extra = m._extra(suf, slens, audios, None)
+        Lout = max(len(ps.prefix) for ps in sessions) + Lmax + int(max_new_tokens)
+        out_ids = torch.zeros(Q, Lout, dtype=torch.long)
+        out_lens = torch.zeros(Q, dtype=torch.int32)
+        out_nseg = torch.zeros(Q, dtype=torch.int32)
+        offs = torch.zeros(Q, dtype=torch.long)
+        height, width = [ps.height for ps in sessions], [ps.width for ps in sessions]
+        cap = sum(m.max_seg * h * w for h, w in zip(height, width))
+        out_masks = torch.empty(cap, device=m.device, dtype=torch.float32)
+        out_low = hid = None
+        if _return_extras:
+            L = 4 * m.cfg.sam.grid
+            out_low = torch.zeros(Q, m.max_seg, L, L, device=m.device, dtype=torch.float32)
+            if _return_extras != "low":
+                hid = torch.empty(Q, m.cfg.llm.max_seq, m.cfg.llm.dim, device=m.device, dtype=torch.float32)
+        eos = m.config.eos_token_id if m.config.eos_token_id is not None else -1
+        if draft_ids is not None:
+            drafts = normalize_drafts(draft_ids, Q)
+            if any(drafts):
+                m.set_draft(drafts)
+        m._check(m.lib.anyref_session_generate_pooled(
+            m.h, m._stream(), _ptr(slots), _ptr(suf), _ptr(slens), Q, Lmax, _ptr(extra), _ptr(eslots), n_extra,
+            int(max_new_tokens), int(eos), _ptr(out_ids), _ptr(out_lens), _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs),
+            _ptr(out_low), _ptr(hid)), "session_generate_pooled")
+        for b, ps in enumerate(sessions):
+            self.table.touch(ps.key)
+            self._held[b] = (ps.slot, ps.gen)
+        res = m._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width, per_row=True)
+        if _return_extras:
+            return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **m.draft_stats(Q))
+        return res
+
+    @torch.no_grad()
+    def generate_many(self, items, max_new_tokens=128, _return_extras: bool = False):
+        """Any number of `(session, ids)` items -- ids a 1-D suffix or full prompt -- answered in calls of at most max_batch rows.
+        -> one `(output_ids [n], pred_masks [nseg, h, w] or None)` per item, in the caller's order (with `_return_extras`, a
+        third entry: a dict with the row's `low_res`, `nseg` and, unless "low", `hidden`).  Items are taken in order, max_batch
+        per call; inside a call an item is given the cache row that already holds its image from the call before where there is
+        one (anyref_amd/session.py `plan_calls`), so that row's gather is skipped."""
+        from .session import plan_calls
+        self._live()
+        items = [(ps, torch.as_tensor(ids).reshape(-1).long()) for ps, ids in items]
+        for ps, _ in items:
+            ps.check()
+        out = [None] * len(items)
+        for order in plan_calls([(ps.slot, ps.gen) for ps, _ in items], self.model.max_batch, self._held):
+            rows = [items[i][1] for i in order]
+            n = max(len(r) for r in rows)
+            ids = torch.zeros(len(rows), n, dtype=torch.long)
+            mask = torch.zeros(len(rows), n, dtype=torch.bool)
+            for b, r in enumerate(rows):
+                ids[b, : len(r)] = r
+                mask[b, : len(r)] = True
+            res, ex = self.generate([items[i][0] for i in order], ids, attention_masks=mask, max_new_tokens=max_new_tokens,
+                                    _return_extras=_return_extras or "low")
+            for b, i in enumerate(order):
+                n_ids, nseg = int(ex["out_lens"][b]), int(ex["nseg"][b])
+                one = (res[0][b, :n_ids], res[1][b] if res[1] is not None and nseg > 0 else None)
+                if _return_extras:
+                    one += (dict(low_res=ex["low_res"][b], nseg=nseg, hidden=None if ex["hidden"] is None else ex["hidden"][b]),)
+                out[i] = one
+        return out
 
 
 def dice_loss(inputs, targets, num_masks, scale=1000, eps=1e-6):

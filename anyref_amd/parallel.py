@@ -9,6 +9,9 @@ image (token ids, [SEG] count, length).  Full-resolution masks are re-created fr
 by the same bilinear postprocess (bit-identical: the resize is per mask), so the 4 MB/mask
 full-res tensors never cross xGMI.  `backend="nccl"` is RCCL on ROCm; the CPU tests drive the
 same code over gloo.
+
+Image sessions and session pools (`model.image_session`, `model.session_pool`) are per-handle state and are not passed on
+by this driver: it shards plain `generate` calls only.  A rank that wants a pool opens one on its own model.
 """
 from __future__ import annotations
 

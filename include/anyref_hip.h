@@ -332,6 +332,66 @@ int anyref_session_generate(anyref_handle* h, void* stream, const int64_t* suffi
 int anyref_session_close(anyref_handle* h);
 
 /*
+ * Session pool: many images resident at once, queries about different images in one call.  A session lives in
+ * the working buffers (row 0 of the KV cache and of the hidden states, image-embedding slot 0), so a handle holds one, every
+ * image switch pays an open, and any plain call ends it.  A pool keeps what anyref_session_open leaves behind OUTSIDE the working
+ * buffers, compactly, in n_slots slots: the K and V prefix rows of every layer [2 * layers][max_prefix_rows][llm_dim] in the cache
+ * element type, the hidden prefix rows [max_prefix_rows][llm_dim] f32, the SAM image embedding, and on the host the prefix ids, P,
+ * the sizes and a generation counter.  A pooled call brings each row's prefix back from its slot with one gather launch
+ * (anyref_op_kv_gather) and then runs as anyref_session_generate does.
+ *
+ * anyref_session_pool_reserve: after anyref_finalize.  Allocates the pool (counted in anyref_device_bytes; a handle that reserves
+ * nothing holds exactly what it held before).  1 <= max_prefix_rows <= llm_max_seq.  Reserving again with the same sizes changes
+ * nothing; with other sizes it is allowed only while every slot is empty (never stored, closed or lost); n_slots = 0,
+ * max_prefix_rows = 0 frees the pool whatever it holds.  Waits for the device before it frees.
+ */
+int anyref_session_pool_reserve(anyref_handle* h, int n_slots, int max_prefix_rows);
+/*
+ * Copy the live session (anyref_session_open) into `slot`: its cache row, its hidden rows and image-embedding slot 0, by the
+ * gather kernel in its pack direction (one launch for K and V of every layer, one for the hidden rows, one for the embedding).
+ * Replaces whatever the slot held, under a new generation.  The live session stays live and unchanged.
+ * Refused with nothing queued: no live session ("session lost: ended by <entry>" / "no session open"), P > max_prefix_rows, slot
+ * outside the pool, no pool.
+ */
+int anyref_session_store(anyref_handle* h, void* stream, int slot);
+/*
+ * anyref_session_generate for rows about DIFFERENT images: its arguments plus
+ *   slots i32 [Q] host: the slot query b is about.  Rows may name one slot several times or different slots; slots may have
+ *              different P.
+ * Schedule: (1) one gather launch brings every row's K / V prefix, all layers, from its slot into cache row b; two more launches of
+ * the same kernel bring the hidden prefix rows into hidden row b and the image embedding into image-embedding slot b.  The host
+ * remembers which (slot, generation) every cache row and embedding slot holds and skips the rows that already hold the right
+ * prefix (queries only ever write positions >= P); every entry that ends a session, anyref_session_open and
+ * anyref_session_generate clear that memory.  (2) anyref_session_generate's steps from the suffix embeddings on, with
+ * pos0[b] = P[slots[b]], slen[b] = P[slots[b]] + lens[b], every row's own sizes, and the masks decoded against embedding slot b.
+ *   out_ids   i64 [Q, Lout] host, Lout = np + Lmax + max_new_tokens with np the LONGEST prefix_len among the call's slots: row b
+ *              is that slot's prefix_ids + suffix + new tokens from column 0 on, zero behind; out_lens counts all three
+ *   out_hidden rows [0, P[slots[b]]) of query b are its slot's prefix rows
+ * A row's answer does not depend on the other rows: a call about slots [a, b, c] gives row by row what the calls about one slot
+ * with the same Q and lens give.  anyref_set_draft, anyref_draft_stats and anyref_set_rephrase_paths as in
+ * anyref_session_generate.  The call writes row 0: it ends an unpooled live session ("session lost: ended by
+ * anyref_session_generate_pooled").
+ * Refused before anything is queued, the pool and a live session staying usable: a slot outside the pool, empty, or lost ("slot N
+ * lost: ended by <entry>"); Q outside [1, max_batch]; P[slots[b]] + lens[b] + max_new_tokens > llm_max_seq; and
+ * anyref_session_generate's own rules (lens[b] < 1, an image placeholder inside a suffix, an id without an extra row,
+ * rephrase_weight > 0 with the paths switch off).
+ * What ends a slot is what changes the weights: anyref_adapter_apply, anyref_update_weight, anyref_finalize.  anyref_generate and
+ * every other entry that merely uses the working buffers does NOT: the next pooled call gathers again.
+ */
+int anyref_session_generate_pooled(anyref_handle* h, void* stream, const int32_t* slots, const int64_t* suffix_ids,
+                                   const int32_t* lens, int Q, int Lmax, const float* extra_embeds, const int32_t* extra_slots,
+                                   int n_extra, int max_new_tokens, int eos_token_id, int64_t* out_ids, int32_t* out_lens,
+                                   int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
+                                   float* out_low, float* out_hidden);
+/* Empty one slot (also one that was lost).  Error if slot is outside the pool. */
+int anyref_session_slot_close(anyref_handle* h, int slot);
+/* Any pointer may be NULL.  slots, slots in use, bytes the pool holds on the device; cache rows the last pooled call gathered and
+ * skipped; device time of that call's gather launches in ms between two events on its stream (waits for them; -1 when the call
+ * launched none). */
+int anyref_session_pool_stats(anyref_handle* h, int32_t* slots, int32_t* in_use, int64_t* bytes, int32_t* rows_gathered,
+                              int32_t* rows_skipped, double* last_gather_ms);
+
+/*
  * Adapter hot-swap: the reference's evaluations load a LoRA adapter each (`lora_name`), and a training run is
  * evaluated by sweeping its checkpoints (eval_reason.py:188-201).  A handle that RESERVED its LoRA targets before anyref_finalize
  * keeps their unmerged base and can be switched between adapters, and back to the base, any number of times without drift and

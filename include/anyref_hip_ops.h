@@ -82,6 +82,16 @@ int anyref_op_draft_accept(void* stream, const float* logits, int B, int k, int 
  * Error if P > maxS, r0 < 1 or r1 > rows. */
 int anyref_op_kv_broadcast(void* stream, void* kc, void* vc, int layers, int rows, int maxS, int row_elems, int elem_size,
                            int P, int r0, int r1);
+/* per-row gather / pack of a session pool (anyref_session_generate_pooled / anyref_session_store): kc and vc (vc may be NULL: one
+ * buffer) are working buffers [layers][rows][maxS][row_elems] as above, pool is [n_slots][planes][maxP][row_elems] with planes =
+ * layers, or 2 * layers when vc is given (K planes first).  table i32 [n, 4] host: (slot, P, row, skip) per item.  pack == 0: in
+ * every plane, positions [0, P) of pool slot `slot` are copied to row `row`; pack != 0: the other way.  Everything else, on both
+ * sides, is left as it was.  One launch for all planes and up to 16 items; items with P == 0 or skip != 0 move nothing.  The
+ * kernel moves bytes (16 at a time when row_elems * elem_size is a multiple of 16, else 2) and never interprets them.
+ * Error, with nothing launched: slot outside [0, n_slots), row outside [0, rows), P > maxP or P > maxS, two moved items with the
+ * same row (gather) or the same slot (pack). */
+int anyref_op_kv_gather(void* stream, void* kc, void* vc, int layers, int rows, int maxS, void* pool, int n_slots, int maxP,
+                        int row_elems, int elem_size, const int32_t* table, int n, int pack);
 /* LayerNorm (rms=0) / RMSNorm (rms=1); x f32, y f32 */
 int anyref_op_norm(int t, void* stream, const float* x, const float* gain, const float* bias, float* y, int M,
                    int D, float eps, int rms);
