@@ -104,6 +104,8 @@ SYMBOLS = {
     "anyref_llm_extend": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "anyref_set_draft": (_I, [_P, _P, _P, _I, _I]),
     "anyref_draft_stats": (_I, [_P, _P, _P, _I, _P, _P]),
+    "anyref_set_token_scores": (_I, [_P, _I]),
+    "anyref_token_scores": (_I, [_P, _I, _I, _P, _P, _P]),
     "anyref_session_open": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
     "anyref_session_generate": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
     "anyref_session_close": (_I, [_P]),
@@ -169,6 +171,7 @@ SYMBOLS = {
     "anyref_op_rephrase_chain": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _F, _F, _P]),
     "anyref_op_rope_cache": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "anyref_op_argmax": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "anyref_op_token_scores": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "anyref_op_draft_accept": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_kv_broadcast": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),
     "anyref_op_kv_gather": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I]),

@@ -163,6 +163,12 @@ int anyref_draft_stats(anyref_handle* h, int32_t* offered, int32_t* accepted, in
   GUARD(h, h->m->draft_stats(offered, accepted, B, decode_steps, verify_passes));
 }
 
+int anyref_set_token_scores(anyref_handle* h, int on) { GUARD(h, h->m->set_token_scores(on != 0)); }
+
+int anyref_token_scores(anyref_handle* h, int B, int n_cap, float* logprob, float* gap, int32_t* n) {
+  GUARD(h, h->m->token_scores(B, n_cap, logprob, gap, n));
+}
+
 int anyref_adapter_reserve(anyref_handle* h, uint32_t targets) { GUARD(h, h->m->adapter_reserve(targets)); }
 
 int anyref_adapter_apply(anyref_handle* h, void* stream, const anyref_lora_pair* pairs, int n_pairs, float scaling) {

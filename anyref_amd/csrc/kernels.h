@@ -438,6 +438,12 @@ void launch_argmax(const float* x, int M, int N, int ldx, int64_t* out, hipStrea
 // b * maxS + pos[b], kvlen[b] = pos[b] + 1; table dtype 0 = f32, 1 = bf16, 2 = f16
 void launch_argmax_next(const float* x, int M, int N, int ldx, int64_t* out, int* pos, const void* table, int dtype,
                         int D, int maxS, float* x_next, int* row_map, int* kvlen, hipStream_t s);
+// Token scores of logits f32 rows [M, N] (row stride ldx; N >= 2): with id = the row's argmax by the order above,
+// logprob = x[id] - logsumexp(x) and gap = x[id] - max_{i != id} x[i] (0 on a tie).  Row i writes index dst[i] of logprob / gap /
+// id (id may be NULL); dst == NULL: index i; dst[i] < 0: the row is skipped unread.  A kernel of its own, one workgroup per row,
+// one pass, no atomics (token_scores_kernel, ops.hip; the rule: anyref_amd/scores.py).
+void launch_token_scores(const float* logits, int M, int N, int ldx, const int32_t* dst, float* logprob, float* gap,
+                         int64_t* id, hipStream_t s);
 // Accept step of the draft-verified greedy decode: logits f32 [B * k, N] (row stride ldx) of a verification pass that fed
 // draft i64 [B, k] (dlen[b] <= k valid ids per row) behind next[b].  p i64 [B * k] receives the row argmaxes; per row, with
 // g[0] = next[b] and g[j + 1] = p[j], accepted[b] = m = leading j < dlen[b] with g[j] == draft[j]; tokens i64 [B, k + 1] gets

@@ -190,6 +190,23 @@ class ModelBase {
     if (decode_steps) *decode_steps = stat_steps_;
     if (verify_passes) *verify_passes = stat_passes_;
   }
+  // ---- token scores (anyref_set_token_scores / anyref_token_scores) ----
+  // off (default): no launch, no allocation, the decode graphs of a handle that never heard of the switch.  The first
+  // switch-on allocates sc_lp_ / sc_gap_ f32 [max_batch, llm_max_seq] -- indexed like hidden_all_, by the position of the row
+  // that predicted the token -- the first token's dst map sc_dst_ i32 [max_batch], and their pinned host images
+  void set_token_scores(bool on);
+  // of the last generating call (decode_loop's copies, waited for here): row b's sc_n_[b] pairs in generation order
+  void token_scores(int B, int n_cap, float* logprob, float* gap, int32_t* n);
+  // every generating entry: the host state of the call before is gone
+  void scores_clear(int B) { sc_n_.assign(scores_on_ && B > 0 ? B : 0, 0); }
+  bool scores_on_ = false;
+  float *sc_lp_ = nullptr, *sc_gap_ = nullptr;  // device
+  int* sc_dst_ = nullptr;                       // device [max_batch]: b * llm_max_seq + slen[b] - 1 (the first token's rows)
+  float* sc_host_ = nullptr;                    // pinned: logprob [max_batch, llm_max_seq] | gap [same]
+  int* sc_stage_ = nullptr;                     // pinned image of sc_dst_
+  void* sc_ev_ = nullptr;                       // hipEvent_t behind the last call's copies to sc_host_
+  bool sc_pending_ = false;
+  std::vector<int> sc_n_;                       // tokens per row of the last call; row b's pairs lead row b of sc_host_
   std::vector<std::vector<int64_t>> draft_ids_;  // per row; empty: nothing pending
   std::vector<int> stat_offered_, stat_accepted_;  // of the last generate
   int stat_steps_ = 0, stat_passes_ = 0;

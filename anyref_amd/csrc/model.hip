@@ -32,6 +32,49 @@ ModelBase::~ModelBase() {
   if (wcount_) (void)hipFree(wcount_);
   if (pool_ev0_) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(pool_ev0_));
   if (pool_ev1_) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(pool_ev1_));
+  if (sc_ev_) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(sc_ev_));
+  if (sc_host_) (void)hipHostFree(sc_host_);
+  if (sc_stage_) (void)hipHostFree(sc_stage_);
+}
+
+void ModelBase::set_token_scores(bool on) {
+  if (on && !sc_lp_) {
+    HIP_TRY(hipSetDevice(device_));
+    const size_t MB = cfg.max_batch, R = MB * (size_t)cfg.llm_max_seq;
+    HIP_TRY(hipHostMalloc((void**)&sc_host_, sizeof(float) * 2 * R));
+    HIP_TRY(hipHostMalloc((void**)&sc_stage_, sizeof(int) * MB));
+    hipEvent_t ev = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    sc_ev_ = ev;
+    sc_gap_ = reinterpret_cast<float*>(dalloc(R * sizeof(float)));
+    sc_dst_ = reinterpret_cast<int*>(dalloc(MB * sizeof(int)));
+    sc_lp_ = reinterpret_cast<float*>(dalloc(R * sizeof(float)));  // (last: it marks the allocation as done)
+  }
+  if (on != scores_on_) sc_n_.clear();  // what the other setting left is not this one's
+  scores_on_ = on;
+}
+
+void ModelBase::token_scores(int B, int n_cap, float* logprob, float* gap, int32_t* n) {
+  if (!scores_on_)
+    throw std::runtime_error("anyref_token_scores: token scores are off (anyref_set_token_scores(h, 1) before the generating call)");
+  if (B < 0 || n_cap < 0 || !n || (B > 0 && n_cap > 0 && (!logprob || !gap)))
+    throw std::runtime_error("anyref_token_scores: bad B / n_cap or null argument");
+  if (sc_pending_) {
+    HIP_TRY(hipSetDevice(device_));
+    HIP_TRY(hipEventSynchronize(reinterpret_cast<hipEvent_t>(sc_ev_)));
+    sc_pending_ = false;
+  }
+  const size_t S = cfg.llm_max_seq, R = (size_t)cfg.max_batch * S;
+  for (int b = 0; b < B; ++b)
+    if (b < (int)sc_n_.size() && sc_n_[b] > n_cap) throw std::runtime_error("anyref_token_scores: a row holds more than n_cap tokens");
+  for (int b = 0; b < B; ++b) {
+    const int nb = b < (int)sc_n_.size() ? sc_n_[b] : 0;
+    n[b] = nb;
+    for (int g = 0; g < nb; ++g) {
+      logprob[(size_t)b * n_cap + g] = sc_host_[b * S + g];
+      gap[(size_t)b * n_cap + g] = sc_host_[R + b * S + g];
+    }
+  }
 }
 
 void ModelBase::session_pool_stats(int32_t* slots, int32_t* in_use, int64_t* bytes, int32_t* gathered, int32_t* skipped,
@@ -1731,7 +1774,8 @@ void Model<T, TS>::decode_step_graph(hipStream_t s, int B, bool keep_q, bool cor
   }
   // with kernel-side timestamps on, the step is a graph of its own: its GEMVs carry their stamp slots
   const bool stamped = stamp.on;
-  const int key = B * 8 + (corun && corun_grid > 0 ? 4 : 0) + (keep_q ? 2 : 0) + (stamped ? 1 : 0);
+  // (token scores on: the step ends with one more launch, so it is a graph of its own; those of the other setting are kept)
+  const int key = B * 16 + (scores_on_ ? 8 : 0) + (corun && corun_grid > 0 ? 4 : 0) + (keep_q ? 2 : 0) + (stamped ? 1 : 0);
   auto it = decode_graphs_.find(key);
   if (it == decode_graphs_.end()) {
     if (keep_q) ensure_q_last();
@@ -2012,6 +2056,9 @@ void Model<T, TS>::llm_decode_step(hipStream_t s, int B, bool keep_q) {
   h.ldy = c.llm_vocab; h.B = B; h.N = c.llm_vocab; h.K = H;
   h.xn_out = hidden_all_; h.xn_row_map = rowmap_dev_; h.xn_ld = H;
   launch_gemv<T>(h, s);
+  // token scores of the row that decides this step's token, filed under the position of the hidden row that predicted it:
+  // rowmap_dev_[b] = b * S + pos[b] still names that row here (pos[b] - 1 once the argmax below has bumped it)
+  if (scores_on_) launch_token_scores(l_logits_, B, c.llm_vocab, c.llm_vocab, rowmap_dev_, sc_lp_, sc_gap_, nullptr, s);
   // argmax, pos += 1, and the next step's embedding row / cache row index / key count
   launch_argmax_next(l_logits_, B, c.llm_vocab, c.llm_vocab, next_dev_, pos_dev_, emb_table_, kEmbDtype, H, S, d_x_,
                      rowmap_dev_, kvlen_dev_, s);
@@ -2144,6 +2191,9 @@ void Model<T, TS>::draft_verify(hipStream_t s, int B, const std::vector<int>& sl
     if (k[b] > 0)
       launch_convert<T>(hidden_all_ + ((size_t)b * S + slen[b]) * H, H, l_h_ + (size_t)b * n * apad<T>(H), apad<T>(H), k[b], H, s);
   gemm(s, l_h_, H, lm_head_, drf_logits_, V, B * n, ACT_NONE, true);
+  // token scores of the pass's rows: row (b, j) predicted the token behind d[j] from hidden row slen[b] + j, which is what
+  // e.hid_rows maps it to (-1, skipped, for the padding rows j >= k[b]); a rejected position is rewritten by the step that redoes it
+  if (scores_on_) launch_token_scores(drf_logits_, B * n, V, V, e.hid_rows, sc_lp_, sc_gap_, nullptr, s);
   launch_draft_accept(drf_logits_, B, n, V, V, drf_p_, drf_ids_, e.lens, next_dev_, pos_dev_, drf_tok_, drf_acc_, emb_table_,
                       kEmbDtype, H, S, d_x_, rowmap_dev_, kvlen_dev_, s);
   int64_t* tok_h = drf_host_ + (size_t)c.max_batch * kDraftCap;
@@ -2639,6 +2689,7 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
   draft.swap(draft_ids_);
   HIP_TRY(hipSetDevice(device_));
   const anyref_config& c = cfg;
+  scores_clear(B);
   stat_offered_.assign(B > 0 ? B : 0, 0);
   stat_accepted_.assign(B > 0 ? B : 0, 0);
   stat_steps_ = stat_passes_ = 0;
@@ -2781,6 +2832,11 @@ void Model<T, TS>::decode_loop(hipStream_t s, int B, const std::vector<int>& sle
     h.x = l_xlast_; h.ldx = H; gemv_w(h, lm_head_); h.y = l_logits_; h.ldy = c.llm_vocab; h.B = B; h.N = c.llm_vocab;
     h.K = H;
     launch_gemv<T>(h, s);
+    if (scores_on_) {  // the first token's scores, under hidden row slen[b] - 1 (sc_stage_ is free: every loop waits for this token)
+      for (int b = 0; b < B; ++b) sc_stage_[b] = b * S + slen[b] - 1;
+      HIP_TRY(hipMemcpyAsync(sc_dst_, sc_stage_, B * 4, hipMemcpyHostToDevice, s));
+      launch_token_scores(l_logits_, B, c.llm_vocab, c.llm_vocab, sc_dst_, sc_lp_, sc_gap_, nullptr, s);
+    }
     launch_argmax_next(l_logits_, B, c.llm_vocab, c.llm_vocab, next_dev_, pos_dev_, emb_table_, kEmbDtype, H, S, d_x_,
                        rowmap_dev_, kvlen_dev_, s);
   }
@@ -2899,6 +2955,21 @@ void Model<T, TS>::decode_loop(hipStream_t s, int B, const std::vector<int>& sle
       decode_step_graph(s, B, keep_q, corun_step());
       if (fed) sam_feed(sam_next_blk_ + per_step, true);
     }
+  }
+  // token scores: token g of row b sits under hidden row slen[b] + g - 1 (a row that ended early went on stepping past its
+  // last token, never over it).  The copies are queued behind the loop and add no synchronisation to the call: the read
+  // (token_scores) waits for sc_ev_
+  if (scores_on_) {
+    const size_t R = (size_t)c.max_batch * S;
+    for (int b = 0; b < B; ++b) {
+      const size_t n_b = gen[b].size(), src = (size_t)b * S + slen[b] - 1;
+      if (n_b == 0) continue;
+      HIP_TRY(hipMemcpyAsync(sc_host_ + (size_t)b * S, sc_lp_ + src, n_b * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(sc_host_ + R + (size_t)b * S, sc_gap_ + src, n_b * 4, hipMemcpyDeviceToHost, s));
+      sc_n_[b] = (int)n_b;
+    }
+    HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(sc_ev_), s));
+    sc_pending_ = true;
   }
 }
 
@@ -3069,6 +3140,7 @@ void Model<T, TS>::session_core(hipStream_t s, const int32_t* slots, const int64
   const anyref_config& c = cfg;
   const bool pooled = slots != nullptr;
   const std::string who = pooled ? "session_generate_pooled: " : "session_generate: ";
+  scores_clear(nq);
   stat_offered_.assign(nq > 0 ? nq : 0, 0);
   stat_accepted_.assign(nq > 0 ? nq : 0, 0);
   stat_steps_ = stat_passes_ = 0;

@@ -1258,6 +1258,147 @@ void launch_argmax_next(const float* x, int M, int N, int ldx, int64_t* out, int
   hipLaunchKernelGGL(argmax_kernel, dim3(M), dim3(1024), 0, s, x, N, ldx, out, pos, nx);
 }
 
+// Token scores (the rule is anyref_amd/scores.py): for the logits row that decided a token,
+//   id = argmax by argmax_kernel's order, logprob = x[id] - logsumexp(x), gap = x[id] - max_{i != id} x[i].
+// A kernel of its own beside argmax_kernel (which stays as it is): one 1024-thread workgroup per row, one pass.  The row is
+// cut into a scalar head (up to the first 16-byte boundary: ldx = 32007 leaves every row after the first unaligned), a body
+// of 16-byte loads all issued before the first compare, and a scalar tail.  Every thread keeps
+//   (best, bi, second): the greatest value by the argmax order, its index, and the greatest value at any OTHER index, and
+//   (m, s): a running maximum and sum_i exp(x_i - m) over its elements (per 32-element chunk: maximum first, then one exp
+//           per element, the sum so far rescaled once).
+// Both are merged with 6 xor-shuffle levels inside the wave, then the 16 wave results through LDS by 4 more levels in wave 0
+// -- a fixed tree: no atomics, reruns are bit-identical.  -inf entries add 0 to the sum; a row holding a NaN ends on
+// best = NaN, so logprob = gap = NaN; whatever else IEEE gives stands (a row of -inf: NaN; a +inf in the row: NaN).
+__device__ __forceinline__ void score_take(float v, int i, float& best, int& bi, float& second) {
+  const bool vn = __builtin_isnan(v), bn = __builtin_isnan(best);
+  const bool wins = (vn || bn) ? (vn && (!bn || i < bi)) : (v > best || (v == best && i < bi));
+  if (wins) {
+    second = best;
+    best = v;
+    bi = i;
+  } else {
+    second = fmaxf(second, v);
+  }
+}
+// (b2, i2, s2) into (best, bi, second): the loser's best is the only value of its side that can be the other's runner-up
+__device__ __forceinline__ void score_merge(float b2, int i2, float s2, float& best, int& bi, float& second) {
+  const bool vn = __builtin_isnan(b2), bn = __builtin_isnan(best);
+  const bool wins = (vn || bn) ? (vn && (!bn || i2 < bi)) : (b2 > best || (b2 == best && i2 < bi));
+  if (wins) {
+    second = fmaxf(s2, best);
+    best = b2;
+    bi = i2;
+  } else {
+    second = fmaxf(second, b2);
+  }
+}
+// exp(m - M) for M >= m, with the empty partial (m = -inf, s = 0) scaled by 0 instead of exp(-inf - -inf)
+__device__ __forceinline__ float lse_scale(float m, float M) { return m == -INFINITY ? 0.f : __expf(m - M); }
+__device__ __forceinline__ void lse_merge(float m2, float s2, float& m, float& s) {
+  const float M = fmaxf(m, m2);
+  s = s * lse_scale(m, M) + s2 * lse_scale(m2, M);
+  m = M;
+}
+__device__ __forceinline__ void lse_take(float v, float& m, float& s) {
+  const float M = fmaxf(m, v);
+  if (M == -INFINITY) return;
+  s = s * lse_scale(m, M) + __expf(v - M);
+  m = M;
+}
+__global__ __launch_bounds__(1024) void token_scores_kernel(const float* __restrict__ x, int N, int ldx,
+                                                            const int* __restrict__ dst, float* __restrict__ logprob,
+                                                            float* __restrict__ gap, int64_t* __restrict__ id) {
+  constexpr int NT = 1024, U = 8, NW = NT / 64;  // 8 x 1024 float4: a 32k-entry row in one round trip
+  const int o = dst ? dst[blockIdx.x] : (int)blockIdx.x;
+  if (o < 0) return;  // (the whole workgroup: nothing of the row is read)
+  const float* row = x + (int64_t)blockIdx.x * ldx;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float best = -INFINITY, second = -INFINITY, m = -INFINITY, s = 0.f;
+  int bi = 0x7fffffff;
+  const int to16 = (int)((16 - ((uintptr_t)row & 15)) & 15) >> 2;  // elements in front of the first 16-byte boundary
+  const int head = to16 < N ? to16 : N, n4 = (N - head) >> 2, tail0 = head + n4 * 4;
+  const float4* body = reinterpret_cast<const float4*>(row + head);
+  for (int i0 = 0; i0 < n4; i0 += NT * U) {
+    float4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = i0 + u * NT + tid;
+      v[u] = i < n4 ? body[i] : float4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    }
+    float mc = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = head + (i0 + u * NT + tid) * 4;  // (a filler's index is past the row's: it never beats a real entry)
+      score_take(v[u].x, i, best, bi, second);
+      score_take(v[u].y, i + 1, best, bi, second);
+      score_take(v[u].z, i + 2, best, bi, second);
+      score_take(v[u].w, i + 3, best, bi, second);
+      mc = fmaxf(fmaxf(fmaxf(mc, v[u].x), fmaxf(v[u].y, v[u].z)), v[u].w);
+    }
+    const float M = fmaxf(m, mc);
+    if (M != -INFINITY) {
+      s *= lse_scale(m, M);
+#pragma unroll
+      for (int u = 0; u < U; ++u) s += (__expf(v[u].x - M) + __expf(v[u].y - M)) + (__expf(v[u].z - M) + __expf(v[u].w - M));
+      m = M;
+    }
+  }
+  if (tid < head) {
+    const float v = row[tid];
+    score_take(v, tid, best, bi, second);
+    lse_take(v, m, s);
+  }
+  if (tail0 + tid < N) {
+    const float v = row[tail0 + tid];
+    score_take(v, tail0 + tid, best, bi, second);
+    lse_take(v, m, s);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float b2 = __shfl_xor(best, off, 64), s2 = __shfl_xor(second, off, 64);
+    const int i2 = __shfl_xor(bi, off, 64);
+    score_merge(b2, i2, s2, best, bi, second);
+    const float m2 = __shfl_xor(m, off, 64), e2 = __shfl_xor(s, off, 64);
+    lse_merge(m2, e2, m, s);
+  }
+  __shared__ float sb[NW], ss[NW], sm[NW], se[NW];
+  __shared__ int si[NW];
+  if (lane == 0) {
+    sb[wave] = best;
+    si[wave] = bi;
+    ss[wave] = second;
+    sm[wave] = m;
+    se[wave] = s;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const bool in = lane < NW;
+  best = in ? sb[lane] : -INFINITY;
+  bi = in ? si[lane] : 0x7fffffff;
+  second = in ? ss[lane] : -INFINITY;
+  m = in ? sm[lane] : -INFINITY;
+  s = in ? se[lane] : 0.f;
+#pragma unroll
+  for (int off = NW / 2; off > 0; off >>= 1) {
+    const float b2 = __shfl_xor(best, off, 64), s2 = __shfl_xor(second, off, 64);
+    const int i2 = __shfl_xor(bi, off, 64);
+    score_merge(b2, i2, s2, best, bi, second);
+    const float m2 = __shfl_xor(m, off, 64), e2 = __shfl_xor(s, off, 64);
+    lse_merge(m2, e2, m, s);
+  }
+  if (lane == 0) {
+    const float lse = m + logf(s);
+    logprob[o] = best - lse;
+    gap[o] = best - second;
+    if (id) id[o] = bi;
+  }
+}
+void launch_token_scores(const float* logits, int M, int N, int ldx, const int32_t* dst, float* logprob, float* gap,
+                         int64_t* id, hipStream_t s) {
+  if (M <= 0) return;
+  hipLaunchKernelGGL(token_scores_kernel, dim3(M), dim3(1024), 0, s, logits, N, ldx, dst, logprob, gap, id);
+}
+
 // Accept step of a draft-verified greedy decode.  Row b of the verification pass fed the draft d[0 .. k_b) at
 // positions pos[b] ..; p[i] is the argmax of its logits row i (argmax_kernel above, one workgroup per row).  With g[0] = next[b]
 // (the token prefill chose) and g[j + 1] = p[j], the accepted count m is the number of leading j < k_b with g[j] == d[j]:

@@ -366,6 +366,17 @@ int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_
   });
 }
 
+int anyref_op_token_scores(void* stream, const float* logits, int M, int N, int ldx, const int32_t* dst, float* logprob,
+                           float* gap, int64_t* id) {
+  OP_GUARD({
+    if (!logits || !logprob || !gap) throw std::runtime_error("op_token_scores: null argument");
+    if (M < 1) throw std::runtime_error("op_token_scores: M >= 1 rows");
+    if (N < 2) throw std::runtime_error("op_token_scores: a row needs N >= 2 entries (the gap is to the second one)");
+    if (ldx < N) throw std::runtime_error("op_token_scores: ldx < N");
+    launch_token_scores(logits, M, N, ldx, dst, logprob, gap, id, (hipStream_t)stream);
+  });
+}
+
 int anyref_op_draft_accept(void* stream, const float* logits, int B, int k, int N, int ldx, int64_t* p, const int64_t* draft,
                            const int32_t* draft_lens, int64_t* next, int32_t* pos, int64_t* tokens, int32_t* accepted,
                            const void* table, int dtype, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen) {

@@ -69,7 +69,7 @@ _NEEDS_HANDLE = frozenset({
     "generate", "model_forward_new", "forward", "__call__", "encode_images", "sam_encode", "mask_decode", "llm_forward",
     "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
     "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session", "session_pool",
-    "set_rephrase_paths", "early_masks_done", "load_adapter", "set_adapter"})
+    "set_rephrase_paths", "early_masks_done", "load_adapter", "set_adapter", "set_token_scores", "last_token_scores"})
 
 # the tensors an adapter's `modules_to_save` may carry (train.py:375-387) and anyref_update_weight replaces on a live handle
 _SAVED_EXACT = ("model.embed_tokens.weight", "lm_head.weight", "model.text_hidden_fcs.0.0.weight",
@@ -135,6 +135,9 @@ class AnyRefForCausalLM:
         self._draft_policy: Optional[str] = None     # set_draft_policy
         self._last_answers: Optional[List[List[int]]] = None
         self._session_pool = None                    # the SessionPool this model handed out last (told when its slots are ended)
+        self._scores_on = False                      # set_token_scores
+        self._scores_call = None                     # (rows, max_new_tokens) of the last generating call, read on demand
+        self._scores_many = None                     # generate_many: the entries of its calls, in the caller's item order
         # `from_pretrained` flow: weights are gathered on the host first (base checkpoint, CLIP tower, SAM file,
         # token-row resize, LoRA merge all happen BEFORE `.cuda()` in the callers) and go to HBM in one build
         self._host_sd: Optional[Dict[str, torch.Tensor]] = {} if defer else None
@@ -544,6 +547,43 @@ class AnyRefForCausalLM:
                     "draft_stats")
         return dict(draft_offered=off, draft_accepted=acc, decode_steps=int(steps.value), verify_passes=int(passes.value))
 
+    # ---- token scores (anyref_set_token_scores) ---------------------------------------------------
+    def set_token_scores(self, on: bool):
+        """Per-token confidence of everything generated (default off): with it on, every generated token of
+        `generate`, `ImageSession.generate`, `SessionPool.generate` / `generate_many` carries its log-probability and its
+        top-2 logit gap, computed on the device from the logits row that decided it (`last_token_scores`).  Off: nothing is
+        launched or allocated for it.  What is generated is the same either way."""
+        self._check(self.lib.anyref_set_token_scores(self.h, int(bool(on))), "set_token_scores")
+        self._scores_on = bool(on)
+        self._scores_call = self._scores_many = None
+
+    def _generated(self, rows: int, max_new_tokens: int):
+        """every generating call, after the library returned: whose scores `last_token_scores` reads"""
+        self._scores_call = (int(rows), int(max_new_tokens))
+        self._scores_many = None
+
+    def _read_token_scores(self):
+        if self._scores_call is None:
+            return []
+        B, cap = self._scores_call
+        lp = torch.zeros(B, max(cap, 1), dtype=torch.float32)
+        gap = torch.zeros(B, max(cap, 1), dtype=torch.float32)
+        n = torch.zeros(B, dtype=torch.int32)
+        self._check(self.lib.anyref_token_scores(self.h, B, max(cap, 1), _ptr(lp), _ptr(gap), _ptr(n)), "token_scores")
+        return [dict(logprob=lp[b, : int(n[b])].clone(), gap=gap[b, : int(n[b])].clone()) for b in range(B)]
+
+    def last_token_scores(self):
+        """One entry per row of the last `generate`, `ImageSession.generate`, `SessionPool.generate` or `generate_many` call
+        (there: per item, in the caller's item order): a dict of `logprob` and `gap`, CPU f32 tensors of length n_b aligned
+        with the generated part of `output_ids[b]` -- logprob = x[id] - logsumexp(x), gap = x[id] - the greatest other logit
+        (0 on a tie) of the f32 logits row x that decided the token (anyref_amd/scores.py).  RuntimeError while the switch
+        is off."""
+        if not self._scores_on:
+            raise RuntimeError("last_token_scores: token scores are off (model.set_token_scores(True) before the call)")
+        if self._scores_many is not None:
+            return list(self._scores_many)
+        return self._read_token_scores()
+
     # ---- per-kernel timing for bench.py ------------------------------------------------------
     def profile_enable(self, on: bool, only_tag: Optional[str] = None, sample_every: int = 1):
         self._check(self.lib.anyref_profile_config(self.h, only_tag.encode() if only_tag else None, sample_every),
@@ -892,6 +932,7 @@ class AnyRefForCausalLM:
             self.h, self._stream(), _ptr(clip), _ptr(sam), _ptr(ids), _ptr(lens), B, Lmax, _ptr(extra),
             _ptr(slots), n_extra, _ptr(rs), _ptr(os_), int(max_new_tokens), int(eos), _ptr(out_ids), _ptr(out_lens),
             _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)), "generate")
+        self._generated(B, max_new_tokens)
         if self._draft_policy == "last":
             self._last_answers = [out_ids[b, int(lens[b]): int(out_lens[b])].tolist() for b in range(B)]
         res = self._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width)
@@ -1156,6 +1197,7 @@ class ImageSession:
             m.h, m._stream(), _ptr(suf), _ptr(slens), Q, Lmax, _ptr(extra), _ptr(slots), n_extra, int(max_new_tokens), int(eos),
             _ptr(out_ids), _ptr(out_lens), _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)),
             "session_generate")
+        m._generated(Q, max_new_tokens)
         res = m._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width, per_row=True)
         if _return_extras:
             return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **m.draft_stats(Q))
@@ -1322,6 +1364,7 @@ class SessionPool:
             m.h, m._stream(), _ptr(slots), _ptr(suf), _ptr(slens), Q, Lmax, _ptr(extra), _ptr(eslots), n_extra,
             int(max_new_tokens), int(eos), _ptr(out_ids), _ptr(out_lens), _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs),
             _ptr(out_low), _ptr(hid)), "session_generate_pooled")
+        m._generated(Q, max_new_tokens)
         for b, ps in enumerate(sessions):
             self.table.touch(ps.key)
             self._held[b] = (ps.slot, ps.gen)
@@ -1343,6 +1386,7 @@ class SessionPool:
         for ps, _ in items:
             ps.check()
         out = [None] * len(items)
+        scores = [None] * len(items) if self.model._scores_on else None
         for order in plan_calls([(ps.slot, ps.gen) for ps, _ in items], self.model.max_batch, self._held):
             rows = [items[i][1] for i in order]
             n = max(len(r) for r in rows)
@@ -1353,12 +1397,16 @@ class SessionPool:
                 mask[b, : len(r)] = True
             res, ex = self.generate([items[i][0] for i in order], ids, attention_masks=mask, max_new_tokens=max_new_tokens,
                                     _return_extras=_return_extras or "low")
+            if scores is not None:                # (the next call clears them)
+                for b, e in enumerate(self.model._read_token_scores()):
+                    scores[order[b]] = e
             for b, i in enumerate(order):
                 n_ids, nseg = int(ex["out_lens"][b]), int(ex["nseg"][b])
                 one = (res[0][b, :n_ids], res[1][b] if res[1] is not None and nseg > 0 else None)
                 if _return_extras:
                     one += (dict(low_res=ex["low_res"][b], nseg=nseg, hidden=None if ex["hidden"] is None else ex["hidden"][b]),)
                 out[i] = one
+        self.model._scores_many = scores
         return out
 
 

@@ -285,6 +285,21 @@ int anyref_set_draft(anyref_handle* h, const int64_t* draft_ids, const int32_t* 
 int anyref_draft_stats(anyref_handle* h, int32_t* offered, int32_t* accepted, int B, int32_t* decode_steps,
                        int32_t* verify_passes);
 
+/* Token scores: how sure the greedy decode was of every token it generated.  Off by default; while off
+ * nothing is launched or allocated for it.  On: every generated token of anyref_generate, anyref_session_generate and
+ * anyref_session_generate_pooled -- drafted or not, graphs on or off -- carries two f32 numbers computed on the device from the
+ * f32 logits row x that decided it (token_scores_kernel; anyref_op_token_scores states the rule):
+ *   logprob = x[id] - logsumexp(x)      gap = x[id] - max over i != id of x[i]   (the top-2 logit gap; 0 on a tie)
+ * The first switch-on allocates two f32 arrays [max_batch, llm_max_seq], indexed like the hidden states by the position of
+ * the row that predicted the token.  The decode step's graph is keyed by the switch: graphs captured under one setting are
+ * kept, and never replayed, under the other. */
+int anyref_set_token_scores(anyref_handle* h, int on);
+/* Of the last generating call, for its rows b < B: n[b] = tokens row b generated (its EOS included), and their scores in
+ * generation order at logprob[b * n_cap ..] / gap[b * n_cap ..] (f32 host, [B, n_cap]; entries past n[b] are left alone).
+ * Every generating call clears this state on entry; rows the call did not have report n = 0.  Error while the switch is off,
+ * and if a row holds more than n_cap tokens. */
+int anyref_token_scores(anyref_handle* h, int B, int n_cap, float* logprob, float* gap, int32_t* n);
+
 /*
  * Image sessions: the callers' loops ask several questions about one image (RefCOCO: ~7 expressions per image,
  * one `generate` each with the same clip_images / sam_images, eval_referseg.py:124-137).  Everything that depends only on the

@@ -66,6 +66,13 @@ int anyref_op_rope_cache(int t, void* stream, const void* qkv, const float* slab
  * b * maxS + pos[b], kvlen[b] = pos[b] + 1 (pos required) */
 int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_t* out, int32_t* pos, const void* table,
                      int is_bf16, int D, int maxS, float* x_next, int32_t* row_map, int32_t* kvlen);
+/* token scores (anyref_set_token_scores) of logits f32 rows [M, N] (row stride ldx): with id = the row's argmax as
+ * anyref_op_argmax chooses it, logprob = x[id] - logsumexp(x) and gap = x[id] - max over i != id of x[i] (the top-2 logit gap,
+ * 0 on a tie; the f32 subtraction).  Row i writes index dst[i] of logprob f32 / gap f32 / id i64 (id may be NULL); dst NULL:
+ * index i; dst[i] < 0: the row is skipped without being read and nothing is written for it.  A row holding a NaN gives
+ * logprob = gap = NaN; -inf entries add 0 to the sum.  Error (nothing launched) if M < 1, N < 2 or ldx < N. */
+int anyref_op_token_scores(void* stream, const float* logits, int M, int N, int ldx, const int32_t* dst, float* logprob,
+                           float* gap, int64_t* id);
 /* accept step of the draft-verified greedy decode (anyref_set_draft): logits f32 [B * k, N] (row stride ldx) of a verification
  * pass that fed draft i64 [B, k] (draft_lens[b] <= k valid ids per row, 0 = none) behind next[b], the token already chosen.
  * p i64 [B * k] receives the row argmaxes (first index on ties).  Per row, with g[0] = next[b], g[j + 1] = p[j]: accepted[b] = m =
