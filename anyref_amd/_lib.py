@@ -187,6 +187,25 @@ SYMBOLS = {
     "anyref_op_norm_ex": (_I, [_I, _P, C.POINTER(NormEx)]),
     "anyref_op_attention_ex": (_I, [_I, _P, C.POINTER(AttnEx)]),
     "anyref_op_last_tags": (C.c_char_p, []),
+    # glue kernels and the skinny f32 GEMV (tests/test_gpu_glue_ops.py)
+    "anyref_op_gemv_skinny": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I]),
+    "anyref_op_upscale1": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _F, _P]),
+    "anyref_op_upscale2_masks": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "anyref_op_dense_pe": (_I, [_P, _P, _I, _I, _P]),
+    "anyref_op_build_tokens": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "anyref_op_add_rows": (_I, [_P, _P, _P, _I, _P, _I, _I]),
+    "anyref_op_add_vec": (_I, [_P, _P, _P, _P, _I, _I]),
+    "anyref_op_embed_splice": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _I, _I, _P]),
+    "anyref_op_scatter_rows": (_I, [_P, _P, _P, _P, _I, _P, _I, _I]),
+    "anyref_op_gather_rows": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),
+    "anyref_op_embed_rows": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "anyref_op_im2col_patch": (_I, [_I, _P, _P, _I, _I, _I, _P, _I]),
+    "anyref_op_im2col_3x3": (_I, [_I, _P, _P, _I, _I, _I, _P]),
+    "anyref_op_im2col_conv1": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "anyref_op_clip_assemble": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "anyref_op_l2norm_scale": (_I, [_P, _P, _I, _I, _F, _P]),
+    "anyref_op_to_f32": (_I, [_P, _P, _I, _P, _L]),
+    "anyref_op_dequant_fp8": (_I, [_P, _P, _I, _P, _I, _I, _P, _I]),
 }
 
 _lib = None

@@ -363,8 +363,6 @@ void launch_unsplit(const void* in, int64_t ld_in, float* out, int64_t ld_out, i
                     int f16_terms = 0);
 // out[m, :] = a[m, :] + b[m % bmod, :]   (f32; position embeddings, keys+pe ...)
 void launch_add_rows(const float* a, const float* b, int bmod, float* out, int M, int D, hipStream_t s);
-template <typename T>
-void launch_add_rows_to(const float* a, const float* b, int bmod, void* out, int M, int D, hipStream_t s);
 // CLIP embeddings: x[b,0]=cls+pos[0]; x[b,1+i]=patch[b,i]+pos[1+i]   (f32)
 void launch_clip_assemble(const float* patch, const float* cls, const float* pos, float* x, int B, int n,
                           int D, hipStream_t s, int rows = 0);  // rows > n + 1: zeroed spare rows per item
@@ -424,14 +422,9 @@ struct KvGatherItem {
 constexpr int kKvGatherRows = 16;
 void launch_kv_gather(void* base0, int planes0, void* base1, int planes1, int64_t plane_stride, int rows, int maxS, void* pool,
                       int n_slots, int maxP, int64_t row_bytes, const KvGatherItem* items, int n, bool pack, hipStream_t s);
-// row_map[b] = b*maxS + pos[b]; kvlen[b] = pos[b] + 1
-void launch_decode_index(const int* pos, int B, int maxS, int* row_map, int* kvlen, hipStream_t s);
 // tokens[i, 0:n_out] = out_tokens; tokens[i, n_out] = pred[i]   (mask_decoder.py:127-141)
 void launch_build_tokens(const float* out_tokens, int n_out, const float* pred, int n, int C, float* tokens,
                          hipStream_t s);
-// act[m, j] = silu(gu[m, j]) * gu[m, F + j]
-template <typename T>
-void launch_swiglu(const void* gu, int M, int F, void* out, hipStream_t s);
 // argmax over f32 rows (first index on ties) -> i64
 void launch_argmax(const float* x, int M, int N, int ldx, int64_t* out, hipStream_t s, int* bump = nullptr);
 // argmax, pos[b] += 1, and the next decode step's inputs in the same launch: x_next[b] = table[argmax], row_map[b] =
@@ -467,8 +460,6 @@ void launch_postprocess(const float* low, int64_t lstride, int n, int lh, int lw
                         int W, float* out, hipStream_t s);
 // dense PE table (prompt_encoder.py:189-229): out f32 [g*g, 2*F], gauss f32 [2,F]
 void launch_dense_pe(const float* gauss, int g, int F, float* out, hipStream_t s);
-void launch_fill_i32(int* p, int v, int n, hipStream_t s);
-void launch_add_i32(int* p, int v, int n, hipStream_t s);
 template <typename T>
 void launch_fill_rows_bias(void* dst, int ld, const int* rows, int nrows, const float* bias, int N, hipStream_t s);
 // SURVEY.md §8 f-2 / f-1 (the steps right after / before the path)

@@ -563,17 +563,6 @@ void launch_add_rows(const float* a, const float* b, int bmod, float* out, int M
   const int grid = (int)(cdiv64(total, 256) < 8192 ? cdiv64(total, 256) : 8192);
   hipLaunchKernelGGL((add_rows_kernel<float>), dim3(grid), dim3(256), 0, s, a, b, bmod, out, M, D);
 }
-template <typename T>
-void launch_add_rows_to(const float* a, const float* b, int bmod, void* out, int M, int D, hipStream_t s) {
-  const int64_t total = (int64_t)M * D;
-  if (total <= 0) return;
-  const int grid = (int)(cdiv64(total, 256) < 8192 ? cdiv64(total, 256) : 8192);
-  hipLaunchKernelGGL((add_rows_kernel<T>), dim3(grid), dim3(256), 0, s, a, b, bmod, reinterpret_cast<T*>(out),
-                     M, D);
-}
-template void launch_add_rows_to<float>(const float*, const float*, int, void*, int, int, hipStream_t);
-template void launch_add_rows_to<bf16>(const float*, const float*, int, void*, int, int, hipStream_t);
-template void launch_add_rows_to<f16>(const float*, const float*, int, void*, int, int, hipStream_t);
 
 __global__ void add_vec_kernel(const float* __restrict__ a, const float* __restrict__ v, float* __restrict__ out,
                                int M, int D) {
@@ -1106,17 +1095,6 @@ void launch_kv_gather(void* base0, int planes0, void* base1, int planes1, int64_
       hipLaunchKernelGGL(kv_gather_kernel<unsigned short>, grid, dim3(256), 0, s, pack ? work : pl, pack ? pl : work, t);
   }
 }
-__global__ void decode_index_kernel(const int* __restrict__ pos, int B, int maxS, int* __restrict__ row_map,
-                                    int* __restrict__ kvlen) {
-  const int b = threadIdx.x;
-  if (b < B) {
-    row_map[b] = b * maxS + pos[b];
-    kvlen[b] = pos[b] + 1;
-  }
-}
-void launch_decode_index(const int* pos, int B, int maxS, int* row_map, int* kvlen, hipStream_t s) {
-  hipLaunchKernelGGL(decode_index_kernel, dim3(1), dim3(64), 0, s, pos, B, maxS, row_map, kvlen);
-}
 __global__ void build_tokens_kernel(const float* __restrict__ out_tokens, int n_out, const float* __restrict__ pred,
                                     int C, float* __restrict__ tokens) {
   const int i = blockIdx.y, t = blockIdx.x;
@@ -1129,29 +1107,6 @@ void launch_build_tokens(const float* out_tokens, int n_out, const float* pred, 
   if (n <= 0) return;
   hipLaunchKernelGGL(build_tokens_kernel, dim3(n_out + 1, n), dim3(256), 0, s, out_tokens, n_out, pred, C, tokens);
 }
-
-template <typename T>
-__global__ void swiglu_kernel(const T* __restrict__ gu, int M, int F, T* __restrict__ out) {
-  const int64_t total = (int64_t)M * F;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t m = i / F;
-    const int j = (int)(i % F);
-    const float g = to_f32<T>(gu[m * 2 * F + j]), u = to_f32<T>(gu[m * 2 * F + F + j]);
-    out[i] = from_f32<T>(apply_act(g, ACT_SILU) * u);
-  }
-}
-template <typename T>
-void launch_swiglu(const void* gu, int M, int F, void* out, hipStream_t s) {
-  const int64_t total = (int64_t)M * F;
-  if (total <= 0) return;
-  const int grid = (int)(cdiv64(total, 256) < 8192 ? cdiv64(total, 256) : 8192);
-  hipLaunchKernelGGL((swiglu_kernel<T>), dim3(grid), dim3(256), 0, s, reinterpret_cast<const T*>(gu), M, F,
-                     reinterpret_cast<T*>(out));
-}
-template void launch_swiglu<float>(const void*, int, int, void*, hipStream_t);
-template void launch_swiglu<bf16>(const void*, int, int, void*, hipStream_t);
-template void launch_swiglu<f16>(const void*, int, int, void*, hipStream_t);
 
 // argmax, first index on ties (torch.argmax on CPU returns the first maximal index).  One 1024-thread
 // workgroup per row, 16-byte loads all issued before the first compare (the row is read once, the
@@ -1486,8 +1441,6 @@ void launch_upscale1(const float* tmp, int n, int g, int C, const float* ln_g, c
 }
 template void launch_upscale1<float>(const float*, int, int, int, const float*, const float*, float, void*,
                                      hipStream_t);
-template void launch_upscale1<bf16>(const float*, int, int, int, const float*, const float*, float, void*,
-                                    hipStream_t);
 
 // masks[i,t,Y,X] = sum_c hyper[i,t,c] * gelu(tmp[i, (Y/2,X/2), (Y%2*2+X%2)*C + c]); thread per pixel.
 __global__ void upscale2_masks_kernel(const float* __restrict__ tmp, const float* __restrict__ hyper, int n,
@@ -1583,21 +1536,6 @@ __global__ void dense_pe_kernel(const float* __restrict__ gauss, int g, int F, f
 void launch_dense_pe(const float* gauss, int g, int F, float* out, hipStream_t s) {
   const int64_t total = (int64_t)g * g * F;
   hipLaunchKernelGGL(dense_pe_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, s, gauss, g, F, out);
-}
-
-__global__ void fill_i32_kernel(int* p, int v, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-void launch_fill_i32(int* p, int v, int n, hipStream_t s) {
-  hipLaunchKernelGGL(fill_i32_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p, v, n);
-}
-__global__ void add_i32_kernel(int* p, int v, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] += v;
-}
-void launch_add_i32(int* p, int v, int n, hipStream_t s) {
-  hipLaunchKernelGGL(add_i32_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p, v, n);
 }
 
 // y[:] += w * sum_{j in [s0,e0)} (p[j]/sum p) * X[j,:]

@@ -60,6 +60,17 @@ void by_type(int t, F&& f) {  // f(T()) for the storage type t = 0 .. 4
   else if (t == 4) f(sp16h());
   else throw std::runtime_error("op: t = 0 .. 4");
 }
+// t = 3 / 4 of the im2col entries: the kernel writes pair rows [rows, cols] (cols % 64 == 0) into a temporary whose every 16-bit
+// word starts as a NaN pattern (an element the kernel leaves out comes back as NaN, not as a zero that a pad column should be),
+// out f32 [rows, cols] = hi + lo
+template <typename F>
+void im2col_pairs(int t, int rows, int cols, float* out, hipStream_t st, F&& run) {
+  if (cols % 64) throw std::runtime_error("op_im2col t=3/4: the row length must be a multiple of 64");
+  TmpBuf Ps((size_t)rows * cols * 4);
+  HIP_TRY(hipMemset(Ps.p, 0xFF, (size_t)rows * cols * 4));
+  run(Ps.p);
+  launch_unsplit(Ps.p, cols, out, cols, rows, cols, st, t == 4);
+}
 }  // namespace
 
 extern "C" {
@@ -633,5 +644,165 @@ int anyref_op_kaldi_fbank(void* stream, const float* wave, int C, int T, int win
 int anyref_op_clip_finish(void* stream, const uint8_t* img, int ih, int iw, int y0, int x0, int h, int w, int S,
                           const float* mean3, const float* std3, float* out) {
   OP_GUARD(launch_clip_finish(img, ih, iw, y0, x0, h, w, S, mean3, std3, out, (hipStream_t)stream));
+}
+
+// ---- glue kernels and the skinny f32 GEMV (tests/test_gpu_glue_ops.py) -------------------------------------------------
+int anyref_op_gemv_skinny(void* stream, const float* x, int ldx, const float* W, const float* bias, float* y, int ldy,
+                          const float* resid, int B, int N, int K, int act) {
+  OP_GUARD({
+    if (!x || !W || !y) throw std::runtime_error("op_gemv_skinny: null argument");
+    if (N < 1 || K < 4 || ldx < K || ldy < N) throw std::runtime_error("op_gemv_skinny: N >= 1, K >= 4, ldx >= K, ldy >= N");
+    GemvArgs a;
+    a.x = x; a.ldx = ldx; a.W = W; a.bias = bias; a.y = y; a.ldy = ldy; a.resid = resid; a.B = B; a.N = N; a.K = K; a.act = act;
+    launch_gemv_skinny_f32(a, (hipStream_t)stream);
+  });
+}
+
+int anyref_op_upscale1(int t, void* stream, const float* tmp, int n, int g, int C, const float* ln_g, const float* ln_b, float eps,
+                       void* out) {
+  OP_GUARD({
+    if (t != 0) throw std::runtime_error("op_upscale1: t = 0 (the f32 output is the only form the model runs)");
+    if (n < 1 || g < 1 || C < 1) throw std::runtime_error("op_upscale1: bad shape");
+    launch_upscale1<float>(tmp, n, g, C, ln_g, ln_b, eps, out, (hipStream_t)stream);
+  });
+}
+
+int anyref_op_upscale2_masks(void* stream, const float* tmp, const float* hyper, int n, int ntok, int g2, int C, float* masks) {
+  OP_GUARD({
+    if (n < 1 || ntok < 1 || g2 < 1 || C < 1) throw std::runtime_error("op_upscale2_masks: bad shape");
+    launch_upscale2_masks(tmp, hyper, n, ntok, g2, C, masks, (hipStream_t)stream);
+  });
+}
+
+int anyref_op_dense_pe(void* stream, const float* gauss, int g, int F, float* out) {
+  OP_GUARD({
+    if (g < 1 || F < 1) throw std::runtime_error("op_dense_pe: bad shape");
+    launch_dense_pe(gauss, g, F, out, (hipStream_t)stream);
+  });
+}
+
+int anyref_op_build_tokens(void* stream, const float* out_tokens, int n_out, const float* pred, int n, int C, float* tokens) {
+  OP_GUARD(launch_build_tokens(out_tokens, n_out, pred, n, C, tokens, (hipStream_t)stream));
+}
+
+int anyref_op_add_rows(void* stream, const float* a, const float* b, int bmod, float* out, int M, int D) {
+  OP_GUARD({
+    if (bmod < 1) throw std::runtime_error("op_add_rows: bmod >= 1");
+    launch_add_rows(a, b, bmod, out, M, D, (hipStream_t)stream);
+  });
+}
+
+int anyref_op_add_vec(void* stream, const float* a, const float* v, float* out, int M, int D) {
+  OP_GUARD(launch_add_vec(a, v, out, M, D, (hipStream_t)stream));
+}
+
+int anyref_op_embed_splice(void* stream, const int64_t* ids, const int32_t* lens, int B, int Lmax, const void* table, int dtype,
+                           int vocab, const float* img_feat, int n_img, float* x, int Smax, int D, int32_t* out_len) {
+  OP_GUARD({
+    if (dtype < 0 || dtype > 2) throw std::runtime_error("op_embed_splice: table dtype 0 / 1 / 2");
+    if (B < 1 || Lmax < 1 || n_img < 1 || Smax < 1 || D < 1) throw std::runtime_error("op_embed_splice: bad shape");
+    launch_embed_splice(ids, lens, B, Lmax, table, dtype, vocab, img_feat, n_img, x, Smax, D, out_len, (hipStream_t)stream);
+  });
+}
+
+int anyref_op_scatter_rows(void* stream, const float* rows, const int32_t* dst_b, const int32_t* dst_pos, int n, float* x, int Smax,
+                           int D) {
+  OP_GUARD(launch_scatter_rows(rows, dst_b, dst_pos, n, x, Smax, D, (hipStream_t)stream));
+}
+
+int anyref_op_gather_rows(void* stream, const float* x, int Smax, int D, const int32_t* b, const int32_t* pos, int n, float* out) {
+  OP_GUARD(launch_gather_rows(x, Smax, D, b, pos, n, out, (hipStream_t)stream));
+}
+
+int anyref_op_embed_rows(void* stream, const int64_t* ids, int B, const void* table, int dtype, int D, float* x) {
+  OP_GUARD({
+    if (dtype < 0 || dtype > 2) throw std::runtime_error("op_embed_rows: table dtype 0 / 1 / 2");
+    if (B < 1) throw std::runtime_error("op_embed_rows: B >= 1");
+    launch_embed_rows(ids, B, table, dtype, D, x, (hipStream_t)stream);
+  });
+}
+
+int anyref_op_im2col_patch(int t, void* stream, const float* img, int B, int S, int p, void* out, int Kp) {
+  OP_GUARD({
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 1 || p < 1 || S < p || S % p || Kp < 3 * p * p) throw std::runtime_error("op_im2col_patch: S % p == 0, Kp >= 3 p^2");
+    const int rows = B * (S / p) * (S / p);
+    if (t == 3 || t == 4)
+      im2col_pairs(t, rows, Kp, reinterpret_cast<float*>(out), st, [&](void* ps) {
+        if (t == 4) launch_im2col_patch<sp16h>(img, B, S, p, ps, Kp, st);
+        else launch_im2col_patch<sp16>(img, B, S, p, ps, Kp, st);
+      });
+    else
+      by_type(t, [&](auto T0) {
+        using T = decltype(T0);
+        if constexpr (!is_split<T>::value) launch_im2col_patch<T>(img, B, S, p, out, Kp, st);
+      });
+  });
+}
+
+int anyref_op_im2col_3x3(int t, void* stream, const void* in, int B, int g, int C, void* out) {
+  OP_GUARD({
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 1 || g < 1 || C < 1) throw std::runtime_error("op_im2col_3x3: bad shape");
+    const int rows = B * g * g;
+    if (t == 3 || t == 4) {  // the kernel reads pairs too: in f32 [rows, C] -> pairs
+      if (C % 64) throw std::runtime_error("op_im2col_3x3 t=3/4: C % 64 != 0");
+      TmpBuf Is((size_t)rows * C * 4);
+      if (t == 4) launch_convert<sp16h>(reinterpret_cast<const float*>(in), C, Is.p, C, rows, C, st);
+      else launch_convert<sp16>(reinterpret_cast<const float*>(in), C, Is.p, C, rows, C, st);
+      im2col_pairs(t, rows, 9 * C, reinterpret_cast<float*>(out), st, [&](void* ps) {
+        if (t == 4) launch_im2col_3x3<sp16h>(Is.p, B, g, C, ps, st);
+        else launch_im2col_3x3<sp16>(Is.p, B, g, C, ps, st);
+      });
+    } else
+      by_type(t, [&](auto T0) {
+        using T = decltype(T0);
+        if constexpr (!is_split<T>::value) launch_im2col_3x3<T>(in, B, g, C, out, st);
+      });
+  });
+}
+
+int anyref_op_im2col_conv1(int t, void* stream, const float* img, int n, int Hh, int Ww, int k, int st_, void* out) {
+  OP_GUARD({
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || k < 1 || st_ < 1 || Hh < k || Ww < k) throw std::runtime_error("op_im2col_conv1: bad shape");
+    const int rows = n * ((Hh - k) / st_ + 1) * ((Ww - k) / st_ + 1);
+    if (t == 3 || t == 4)
+      im2col_pairs(t, rows, k * k, reinterpret_cast<float*>(out), st, [&](void* ps) {
+        if (t == 4) launch_im2col_conv1<sp16h>(img, n, Hh, Ww, k, st_, ps, st);
+        else launch_im2col_conv1<sp16>(img, n, Hh, Ww, k, st_, ps, st);
+      });
+    else
+      by_type(t, [&](auto T0) {
+        using T = decltype(T0);
+        if constexpr (!is_split<T>::value) launch_im2col_conv1<T>(img, n, Hh, Ww, k, st_, out, st);
+      });
+  });
+}
+
+int anyref_op_clip_assemble(void* stream, const float* patch, const float* cls, const float* pos, float* x, int B, int n, int D,
+                            int rows) {
+  OP_GUARD({
+    if (B < 1 || n < 1 || D < 1 || (rows > 0 && rows < n + 1)) throw std::runtime_error("op_clip_assemble: rows = 0 or >= n + 1");
+    launch_clip_assemble(patch, cls, pos, x, B, n, D, (hipStream_t)stream, rows);
+  });
+}
+
+int anyref_op_l2norm_scale(void* stream, const float* x, int rows, int D, float scale, float* y) {
+  OP_GUARD(launch_l2norm_scale(x, rows, D, scale, y, (hipStream_t)stream));
+}
+
+int anyref_op_to_f32(void* stream, const void* in, int dtype, float* out, int64_t n) {
+  OP_GUARD({
+    if (dtype < 0 || dtype > 2) throw std::runtime_error("op_to_f32: dtype 0 / 1 / 2");
+    launch_to_f32(in, dtype, out, n, (hipStream_t)stream);
+  });
+}
+
+int anyref_op_dequant_fp8(void* stream, const uint8_t* q, int ldq, const float* scale, int N, int K, void* out_bf16, int ldo) {
+  OP_GUARD({
+    if (ldq < K || ldo < K) throw std::runtime_error("op_dequant_fp8: ldq >= K, ldo >= K");
+    launch_dequant_fp8_rows(q, ldq, scale, N, K, out_bf16, ldo, (hipStream_t)stream);
+  });
 }
 }

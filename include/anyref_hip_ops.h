@@ -1,7 +1,8 @@
 /*
- * anyref_hip_ops.h — kernel-level entry points of libanyref_hip.so used by the parity tests
- * (tests/test_gpu_ops.py) to check every hand-written kernel against the oracle / torch fp32 in
- * isolation.  Not part of the drop-in boundary (that is anyref_hip.h).
+ * anyref_hip_ops.h — kernel-level entry points of libanyref_hip.so used by the op tests (tests/test_gpu_*ops*.py,
+ * tests/test_gpu_gemm_forms.py and the kernel-level parts of the mode suites; tests/test_cpu_glue_ops_ref.py keeps the
+ * ledger of which test file reaches which launcher) to check every hand-written kernel against a float64 / torch
+ * reference in isolation.  Not part of the drop-in boundary (that is anyref_hip.h).
  * `t` selects the storage type: 0 = f32 (MFMA 16x16x4 f32), 1 = bf16 (MFMA 16x16x32 bf16), 3 = split pairs (ANYREF_MODE_PARITY16: f32
  * operands at the interface, carried as two bf16 terms inside; weights bf16; gemm / gemv / norm / attention entries), 2 = f16 (MFMA 16x16x32
  * f16: the SAM image encoder of the perf build and every tower of ANYREF_MODE_PERF_F16; GEMM, GEMV, norm, attention, decode
@@ -260,6 +261,54 @@ typedef struct anyref_attn_ex {
 int anyref_op_attention_ex(int t, void* stream, anyref_attn_ex* e);
 /* the launch tags (kernels.h ProfScope) booked during the last *_ex call of this thread, comma separated */
 const char* anyref_op_last_tags(void);
+
+/* ---- glue kernels and the skinny f32 GEMV (tests/test_gpu_glue_ops.py; references: tests/glue_ops_ref.py) ---- */
+/* launch_gemv_skinny_f32 (every mask-decoder token GEMM, both text_hidden_fcs layers): y[b, n] = act(sum_k x[b, k] W[n, k] +
+ * bias[n]) + resid[b, n]; x f32 rows at stride ldx, W f32 [N, K] contiguous, y / resid f32 rows at stride ldy (resid may be y
+ * or NULL), act as anyref_op_gemm.  The launcher refuses B outside 1 .. 8, K > 4096, K % 4, ldx % 4 and unaligned x / W */
+int anyref_op_gemv_skinny(void* stream, const float* x, int ldx, const float* W, const float* bias, float* y, int ldy,
+                          const float* resid, int B, int N, int K, int act);
+/* first upscaler tail: tmp f32 [n*g*g, 4*C] (col = (dy*2+dx)*C + c) -> out [n, 2g, 2g, C] = gelu(LayerNorm2d over C); t = 0
+ * (f32 out) is the only instantiation; C <= 128 */
+int anyref_op_upscale1(int t, void* stream, const float* tmp, int n, int g, int C, const float* ln_g, const float* ln_b, float eps,
+                       void* out);
+/* second tail: masks f32 [n, ntok, 2*g2, 2*g2] = sum_c hyper[i, t, c] * gelu(tmp[i, (Y/2, X/2), (Y%2*2 + X%2)*C + c]);
+ * hyper f32 [n, ntok, C], ntok <= 8 */
+int anyref_op_upscale2_masks(void* stream, const float* tmp, const float* hyper, int n, int ntok, int g2, int C, float* masks);
+/* dense positional encoding: gauss f32 [2, F] -> out f32 [g*g, 2*F] = sin | cos of 2 pi (cx G[0] + cy G[1]), c = 2 (i + .5) / g - 1 */
+int anyref_op_dense_pe(void* stream, const float* gauss, int g, int F, float* out);
+/* tokens f32 [n, n_out + 1, C]: rows 0 .. n_out-1 = out_tokens [n_out, C], row n_out = pred[i] */
+int anyref_op_build_tokens(void* stream, const float* out_tokens, int n_out, const float* pred, int n, int C, float* tokens);
+/* out[m, :] = a[m, :] + b[m % bmod, :] and out[m, :] = a[m, :] + v[:]   (f32 [M, D]) */
+int anyref_op_add_rows(void* stream, const float* a, const float* b, int bmod, float* out, int M, int D);
+int anyref_op_add_vec(void* stream, const float* a, const float* v, float* out, int M, int D);
+/* LLaVA input assembly: ids i64 [B, Lmax], lens i32 [B], table [vocab, D] of dtype 0 f32 / 1 bf16 / 2 f16, img_feat f32
+ * [B, n_img, D] -> x f32 [B, Smax, D]: the first -200 of a row expands to the n_img image rows, every other id < 0 or >= vocab
+ * gives a zero row, rows >= out_len[b] are left alone; out_len[b] = len (+ n_img - 1 with an image).  At most Smax rows */
+int anyref_op_embed_splice(void* stream, const int64_t* ids, const int32_t* lens, int B, int Lmax, const void* table, int dtype,
+                           int vocab, const float* img_feat, int n_img, float* x, int Smax, int D, int32_t* out_len);
+/* x[dst_b[i], dst_pos[i], :] = rows[i, :];  out[i, :] = x[b[i], pos[i], :];  x[b, :] = table[ids[b], :]   (x f32 [*, Smax, D]) */
+int anyref_op_scatter_rows(void* stream, const float* rows, const int32_t* dst_b, const int32_t* dst_pos, int n, float* x, int Smax,
+                           int D);
+int anyref_op_gather_rows(void* stream, const float* x, int Smax, int D, const int32_t* b, const int32_t* pos, int n, float* out);
+int anyref_op_embed_rows(void* stream, const int64_t* ids, int B, const void* table, int dtype, int D, float* x);
+/* tower front ends, t = 0 .. 4.  out is T [rows, cols] for t = 0 / 1 / 2; for t = 3 / 4 the kernel runs on pair rows (cols % 64
+ * == 0) and out is f32 = hi + lo, as anyref_op_split_roundtrip returns it.
+ * patch: img f32 [B, 3, S, S] -> [B*(S/p)^2, Kp], k = c*p*p + ky*p + kx, columns >= 3 p^2 zero
+ * 3x3:   in T [B, g, g, C] (t = 3 / 4: f32, converted to pairs here; C % 64 == 0) -> [B*g*g, 9*C], k = (ky*3 + kx)*C + c, pad 1
+ * conv1: img f32 [n, Hh, Ww] -> [n*gh*gw, k*k], gh = (Hh - k) / st + 1, patches overlap (st < k) */
+int anyref_op_im2col_patch(int t, void* stream, const float* img, int B, int S, int p, void* out, int Kp);
+int anyref_op_im2col_3x3(int t, void* stream, const void* in, int B, int g, int C, void* out);
+int anyref_op_im2col_conv1(int t, void* stream, const float* img, int n, int Hh, int Ww, int k, int st, void* out);
+/* x f32 [B, rows, D]: x[b, 0] = cls + pos[0], x[b, 1 + i] = patch[b, i] + pos[1 + i], rows n + 1 .. rows - 1 zero (rows = 0: n + 1) */
+int anyref_op_clip_assemble(void* stream, const float* patch, const float* cls, const float* pos, float* x, int B, int n, int D,
+                            int rows);
+/* y[r, :] = x[r, :] / max(||x[r]||_2, 1e-12) * scale   (f32 [rows, D]) */
+int anyref_op_l2norm_scale(void* stream, const float* x, int rows, int D, float scale, float* y);
+/* out f32 [n] = in of dtype 0 f32 / 1 bf16 / 2 f16 */
+int anyref_op_to_f32(void* stream, const void* in, int dtype, float* out, int64_t n);
+/* out bf16 [N, K] (row stride ldo, % 8) = bf16(f32(e4m3 q[n, k]) * scale[n]); q rows ldq bytes apart (% 16), K % 16 == 0 */
+int anyref_op_dequant_fp8(void* stream, const uint8_t* q, int ldq, const float* scale, int N, int K, void* out_bf16, int ldo);
 
 #ifdef __cplusplus
 }
