@@ -333,7 +333,8 @@ def attention_form(ty, q, k, v, scale, *, causal=False, kv_len=None, q_len=None,
                    rel_abs=None, rel_pairs=False, O0=None, loss=None, k_wrong=None, tile=64):
     """float64 attention over the stored q / k / v with the per-element bound of tests/test_gpu_ops.attention_bound64 (the
     same terms: scores (hd + 16) 2^-24 sum |q k| scale, exp within 2^-21 (1 + |s - M|), P rounded to T, P V with one
-    rounding per 4 keys, the output rounding).  Rows >= q_len[b] keep O0 with a zero bound.
+    rounding per 4 keys, the output rounding; t = 0: no 16-bit rounding, P V one f32 rounding per key).  Rows >= q_len[b]
+    keep O0 with a zero bound.
     q_pos0[b]: position of query row 0 (causal over a cache: key j visible iff j <= q_pos0[b] + i); rel_pairs: the bias is
     computed by the t = 3 kernel itself from the tables (pair products: PAIR_MUL of rel_abs more on the scores).
     losses: drop_tile (the last `tile` keys of every row), q_pos0_ignored, k_wrong (keys read from k_wrong: the q columns of the fused
@@ -374,14 +375,19 @@ def attention_form(ty, q, k, v, scale, *, causal=False, kv_len=None, q_len=None,
     m = s.max(-1, keepdim=True).values
     delta = (es + es.masked_fill(mask, 0).amax(-1, keepdim=True) + 2.0 ** -21 * (1 + (s - m).abs())).masked_fill(mask, 0)
     dt = torch.einsum("bhqk,bkhd->bqhd", pr * delta, v.abs()) + (pr * delta).sum(-1).permute(0, 2, 1)[..., None] * o.abs()
-    if ty in (1, 2):
+    if ty == 0:
+        # t = 0: f32 operands on the f32 MFMA, P and the output stay f32 -- the same terms without the two 16-bit roundings;
+        # P V adds one key per f32 MFMA step, so one f32 rounding per key: the figure of
+        # tests/test_gpu_decode_ops.decode_bound for the f32 fallback (proved by tests/test_cpu_attn_peaked_ref.py)
+        bound = dt + 2 * (Sk + 64) * U32 * pv
+    elif ty in (1, 2):
         u = U16[ty]
         bound = dt + u * (pv + 2 * o.abs()) + 2 * (Sk / 4 + 64) * U32 * pv
     else:
         # t = 3: f32 operands multiplied as bf16 PAIRS in three passes (hi hi, hi lo, lo hi).  Each operand is hi + lo + r with
         # |lo| <= 2^-8 |a| and |r| <= 2^-17 |a| (out_round_bound): a product loses lo lo (<= 2^-16 |a b|) and the two
         # residuals (2 x 2^-17 |a b|) = PAIR_MUL = 2^-15 of sum |a b|; three times the f32 roundings of one pass
-        assert ty == 3, "attention_form: t = 1 / 2 / 3"
+        assert ty == 3, "attention_form: t = 0 / 1 / 2 / 3"
         dq = (PAIR_MUL + 2 * (hd + 16) * U32) * torch.einsum("bqhd,bkhd->bhqk", q.abs(), k.abs()) * scale
         if rel_pairs:
             assert rel_abs is not None, "rel_pairs needs rel_abs (sum |q| |R| of the bias dot products)"
@@ -402,7 +408,9 @@ def attention_form(ty, q, k, v, scale, *, causal=False, kv_len=None, q_len=None,
 def attention_emulate(ty, q, k, v, scale, *, causal=False, kv_len=None, q_len=None, q_pos0=None, rel_h=None, rel_w=None,
                       kw=0, O0=None, tile=64):
     """the kernel's arithmetic in f32 torch: f32 scores from the stored operands, online softmax over key tiles of `tile`
-    with P rounded to T before P V, the output rounded to T; rows >= q_len not written"""
+    with P rounded to T before P V, the output rounded to T; rows >= q_len not written.
+    The order is the textbook one (natural exp, the maximum moved by every tile that raises it); the kernels' own lazy rule
+    in log2 units -- which matters once scores are peaked -- is tests/attn_peaked_ref.attention_kernel_order"""
     def mul3(eq, a, b):      # t = 3: three passes over the pair terms; 16-bit types: the one product
         if ty != 3:
             return torch.einsum(eq, rnd(a, ty), rnd(b, ty))
