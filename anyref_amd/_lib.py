@@ -106,6 +106,9 @@ SYMBOLS = {
     "anyref_draft_stats": (_I, [_P, _P, _P, _I, _P, _P]),
     "anyref_set_token_scores": (_I, [_P, _I]),
     "anyref_token_scores": (_I, [_P, _I, _I, _P, _P, _P]),
+    "anyref_set_mask_reports": (_I, [_P, _I, _F]),
+    "anyref_set_packed_masks": (_I, [_P, _P, _L]),
+    "anyref_mask_reports": (_I, [_P, _I, _I, _P, _P, _P]),
     "anyref_session_open": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
     "anyref_session_generate": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
     "anyref_session_close": (_I, [_P]),
@@ -172,6 +175,7 @@ SYMBOLS = {
     "anyref_op_rope_cache": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "anyref_op_argmax": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_token_scores": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "anyref_op_mask_report": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
     "anyref_op_draft_accept": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "anyref_op_kv_broadcast": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),
     "anyref_op_kv_gather": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I]),

@@ -169,6 +169,16 @@ int anyref_token_scores(anyref_handle* h, int B, int n_cap, float* logprob, floa
   GUARD(h, h->m->token_scores(B, n_cap, logprob, gap, n));
 }
 
+int anyref_set_mask_reports(anyref_handle* h, int on, float offset) { GUARD(h, h->m->set_mask_reports(on != 0, offset)); }
+
+int anyref_set_packed_masks(anyref_handle* h, uint32_t* packed_dev, int64_t cap_words) {
+  GUARD(h, h->m->set_packed_masks(packed_dev, cap_words));
+}
+
+int anyref_mask_reports(anyref_handle* h, int B, int seg_cap, int32_t* n, int32_t* rec, int64_t* pack_offsets) {
+  GUARD(h, h->m->mask_reports(B, seg_cap, n, rec, pack_offsets));
+}
+
 int anyref_adapter_reserve(anyref_handle* h, uint32_t targets) { GUARD(h, h->m->adapter_reserve(targets)); }
 
 int anyref_adapter_apply(anyref_handle* h, void* stream, const anyref_lora_pair* pairs, int n_pairs, float scaling) {

@@ -207,6 +207,43 @@ class ModelBase {
   void* sc_ev_ = nullptr;                       // hipEvent_t behind the last call's copies to sc_host_
   bool sc_pending_ = false;
   std::vector<int> sc_n_;                       // tokens per row of the last call; row b's pairs lead row b of sc_host_
+  // ---- mask reports (anyref_set_mask_reports / anyref_set_packed_masks / anyref_mask_reports) ----
+  // off (default): no launch, no allocation.  The first switch-on allocates rep_dev_ i32 [max_batch, max_seg, 8] and its
+  // pinned host image.  The two sites that fill out_masks (early_seg_run, run_tail) launch the report behind their
+  // postprocess; run_tail queues the copy to rep_host_ behind the last of them and mask_reports waits for rep_ev_
+  void set_mask_reports(bool on, float offset);
+  void set_packed_masks(uint32_t* dev, int64_t cap_words) {
+    pack_armed_ = nullptr;
+    pack_armed_cap_ = 0;
+    if (!dev) return;
+    if (!reports_on_) throw std::runtime_error("set_packed_masks: mask reports are off (anyref_set_mask_reports(h, 1, offset) first)");
+    if (cap_words < 0) throw std::runtime_error("set_packed_masks: negative cap_words");
+    pack_armed_ = dev;
+    pack_armed_cap_ = cap_words;
+  }
+  void mask_reports(int B, int seg_cap, int32_t* n, int32_t* rec, int64_t* pack_offsets);
+  // every mask-producing entry: the host state of the call before is gone, and the one-shot packed buffer is taken --
+  // whatever happens below, nothing stays armed
+  void reports_begin(int B) {
+    const size_t rows = reports_on_ && B > 0 ? (size_t)(B < cfg.max_batch ? B : cfg.max_batch) : 0;
+    rep_n_.assign(rows, 0);
+    rep_off_.assign(rows, 0);
+    pack_cur_ = reports_on_ ? pack_armed_ : nullptr;
+    pack_cur_cap_ = pack_armed_cap_;
+    pack_armed_ = nullptr;
+    pack_armed_cap_ = 0;
+  }
+  static int64_t pack_words(int H, int W) { return (int64_t)H * (((int64_t)W + 31) / 32); }
+  bool reports_on_ = false;
+  float rep_offset_ = 1.f;
+  int32_t* rep_dev_ = nullptr;    // device [max_batch, max_seg, 8]
+  int32_t* rep_host_ = nullptr;   // pinned image
+  void* rep_ev_ = nullptr;        // hipEvent_t behind the last call's copy to rep_host_
+  bool rep_pending_ = false;
+  std::vector<int> rep_n_;        // masks per row of the last call
+  std::vector<int64_t> rep_off_;  // pack_offsets of the last call
+  uint32_t *pack_armed_ = nullptr, *pack_cur_ = nullptr;  // for the next call / taken by the running one
+  int64_t pack_armed_cap_ = 0, pack_cur_cap_ = 0;
   std::vector<std::vector<int64_t>> draft_ids_;  // per row; empty: nothing pending
   std::vector<int> stat_offered_, stat_accepted_;  // of the last generate
   int stat_steps_ = 0, stat_passes_ = 0;

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "model.h"
+#include "mask_report.h"
 
 namespace anyref {
 
@@ -35,6 +36,49 @@ ModelBase::~ModelBase() {
   if (sc_ev_) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(sc_ev_));
   if (sc_host_) (void)hipHostFree(sc_host_);
   if (sc_stage_) (void)hipHostFree(sc_stage_);
+  if (rep_ev_) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(rep_ev_));
+  if (rep_host_) (void)hipHostFree(rep_host_);
+}
+
+void ModelBase::set_mask_reports(bool on, float offset) {
+  if (on && (!(offset >= 0.f) || !std::isfinite(offset)))
+    throw std::runtime_error("set_mask_reports: the offset must be finite and >= 0");
+  if (on && !rep_dev_) {
+    HIP_TRY(hipSetDevice(device_));
+    const size_t n = (size_t)cfg.max_batch * cfg.max_seg * 8;
+    HIP_TRY(hipHostMalloc((void**)&rep_host_, sizeof(int32_t) * n));
+    hipEvent_t ev = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    rep_ev_ = ev;
+    rep_dev_ = reinterpret_cast<int32_t*>(dalloc(n * sizeof(int32_t)));  // (last: it marks the allocation as done)
+  }
+  if (on != reports_on_) {  // what the other setting left is not this one's
+    rep_n_.clear();
+    rep_off_.clear();
+  }
+  if (!on) set_packed_masks(nullptr, 0);
+  reports_on_ = on;
+  if (on) rep_offset_ = offset;
+}
+
+void ModelBase::mask_reports(int B, int seg_cap, int32_t* n, int32_t* rec, int64_t* pack_offsets) {
+  if (!reports_on_)
+    throw std::runtime_error("anyref_mask_reports: mask reports are off (anyref_set_mask_reports(h, 1, offset) before the call)");
+  if (B < 0 || seg_cap < 0 || !n || (B > 0 && seg_cap > 0 && !rec))
+    throw std::runtime_error("anyref_mask_reports: bad B / seg_cap or null argument");
+  if (rep_pending_) {
+    HIP_TRY(hipSetDevice(device_));
+    HIP_TRY(hipEventSynchronize(reinterpret_cast<hipEvent_t>(rep_ev_)));
+    rep_pending_ = false;
+  }
+  for (int b = 0; b < B; ++b)
+    if (b < (int)rep_n_.size() && rep_n_[b] > seg_cap) throw std::runtime_error("anyref_mask_reports: a row holds more than seg_cap masks");
+  for (int b = 0; b < B; ++b) {
+    const int nb = b < (int)rep_n_.size() ? rep_n_[b] : 0;
+    n[b] = nb;
+    if (pack_offsets) pack_offsets[b] = b < (int)rep_off_.size() ? rep_off_[b] : 0;
+    for (int k = 0; k < nb * 8; ++k) rec[(size_t)b * seg_cap * 8 + k] = rep_host_[(size_t)b * cfg.max_seg * 8 + k];
+  }
 }
 
 void ModelBase::set_token_scores(bool on) {
@@ -2547,7 +2591,9 @@ void Model<T, TS>::early_seg_run(const PendingEarly& e) {
   const anyref_config& c = cfg;
   const int H = c.llm_dim, slot = early_done_, L = 4 * sam_g_;
   const int64_t hw = (int64_t)e.orig_hw[0] * e.orig_hw[1];
-  if (early_stop_ || slot >= c.max_seg || (slot + 1) * hw > e.cap) {  // run_tail refuses the call with the proper message
+  const int64_t pw = pack_words(e.orig_hw[0], e.orig_hw[1]);
+  if (early_stop_ || slot >= c.max_seg || (slot + 1) * hw > e.cap ||
+      (pack_cur_ && (slot + 1) * pw > pack_cur_cap_)) {  // run_tail refuses the call with the proper message
     early_stop_ = true;
     return;
   }
@@ -2564,6 +2610,9 @@ void Model<T, TS>::early_seg_run(const PendingEarly& e) {
   mask_decoder(s2_, sam_emb_, pred_emb_ + (size_t)slot * c.out_dim, 1, nullptr, nullptr);
   launch_postprocess(m_masks_, (int64_t)c.num_mask_tokens * L * L, 1, L, L, c.sam_img, e.resized_hw[0], e.resized_hw[1],
                      e.orig_hw[0], e.orig_hw[1], e.out_masks + slot * hw, s2_);
+  if (reports_on_)  // record (0, slot) and its packed words, from the plane just written
+    launch_mask_report(e.out_masks + slot * hw, 1, e.orig_hw[0], e.orig_hw[1], rep_offset_, rep_dev_ + (size_t)slot * 8,
+                       pack_cur_ ? pack_cur_ + slot * pw : nullptr, s2_);
   if (e.out_low)
     HIP_TRY(hipMemcpyAsync(e.out_low + (size_t)slot * L * L, m_masks_, (size_t)L * L * 4, hipMemcpyDeviceToDevice, s2_));
   HIP_TRY(hipEventRecord(ev_sam_, s2_));  // the join now waits for this mask too
@@ -2601,8 +2650,33 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
     off += (int64_t)out_nseg[b] * orig_hw[2 * b] * orig_hw[2 * b + 1];
   }
   if (off > out_masks_cap) throw std::runtime_error("out_masks capacity too small");
+  std::vector<int64_t> pack_off(B, 0);
+  int64_t pack_total = 0;
+  for (int b = 0; b < B; ++b) {
+    pack_off[b] = pack_total;
+    pack_total += out_nseg[b] * pack_words(orig_hw[2 * b], orig_hw[2 * b + 1]);
+  }
+  if (pack_cur_ && pack_total > pack_cur_cap_)
+    throw std::runtime_error("packed masks capacity too small: the call's masks take " + std::to_string(pack_total) +
+                             " words, cap_words is " + std::to_string(pack_cur_cap_));
   if (done > nseg) throw std::runtime_error("internal: more early [SEG] masks than [SEG] tokens");
-  if (nseg == done) return;
+  // mask reports: the records of every row -- the early ones too, `s` has joined their stream -- go to the pinned image
+  // behind the last report; the read (mask_reports) waits for rep_ev_, the call gains no synchronisation
+  auto reports_done = [&]() {
+    if (!reports_on_) return;
+    if (nseg > 0)
+      HIP_TRY(hipMemcpyAsync(rep_host_, rep_dev_, (size_t)B * c.max_seg * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(rep_ev_), s));
+    rep_pending_ = true;
+    for (int b = 0; b < B && b < (int)rep_n_.size(); ++b) {
+      rep_n_[b] = out_nseg[b];
+      rep_off_[b] = pack_off[b];
+    }
+  };
+  if (nseg == done) {
+    reports_done();
+    return;
+  }
   {
     StageScope stage_scope(this, ST_SEG, s);
     for (int i = 0; i < nseg; ++i) {
@@ -2668,6 +2742,10 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
       launch_postprocess(m_masks_, (int64_t)c.num_mask_tokens * L * L, n - j0, L, L, c.sam_img, resized_hw[2 * b],
                          resized_hw[2 * b + 1], orig_hw[2 * b], orig_hw[2 * b + 1], out_masks + mask_offsets[b] + j0 * hw,
                          s);
+      if (reports_on_)  // records (b, j >= j0) and their packed words, from the planes just written
+        launch_mask_report(out_masks + mask_offsets[b] + j0 * hw, n - j0, orig_hw[2 * b], orig_hw[2 * b + 1], rep_offset_,
+                           rep_dev_ + ((size_t)b * c.max_seg + j0) * 8,
+                           pack_cur_ ? pack_cur_ + pack_off[b] + j0 * pack_words(orig_hw[2 * b], orig_hw[2 * b + 1]) : nullptr, s);
       if (out_low)
         for (int j = j0; j < n; ++j)
           HIP_TRY(hipMemcpyAsync(out_low + ((size_t)b * c.max_seg + j) * L * L,
@@ -2676,6 +2754,7 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
     }
     row += n;
   }
+  reports_done();
 }
 
 template <typename T, typename TS>
@@ -2690,6 +2769,7 @@ void Model<T, TS>::generate(hipStream_t s, const float* clip_images, const float
   HIP_TRY(hipSetDevice(device_));
   const anyref_config& c = cfg;
   scores_clear(B);
+  reports_begin(B);
   stat_offered_.assign(B > 0 ? B : 0, 0);
   stat_accepted_.assign(B > 0 ? B : 0, 0);
   stat_steps_ = stat_passes_ = 0;
@@ -3141,6 +3221,7 @@ void Model<T, TS>::session_core(hipStream_t s, const int32_t* slots, const int64
   const bool pooled = slots != nullptr;
   const std::string who = pooled ? "session_generate_pooled: " : "session_generate: ";
   scores_clear(nq);
+  reports_begin(nq);
   stat_offered_.assign(nq > 0 ? nq : 0, 0);
   stat_accepted_.assign(nq > 0 ? nq : 0, 0);
   stat_steps_ = stat_passes_ = 0;
@@ -3317,6 +3398,7 @@ void Model<T, TS>::forward_teacher(hipStream_t s, const float* clip_images, cons
                                int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
                                float* out_low, float* out_hidden, float* out_logits) {
   draft_ids_.clear();  // a draft is a hint for generate: a teacher-forced call in between drops it
+  reports_begin(B);
   HIP_TRY(hipSetDevice(device_));
   const anyref_config& c = cfg;
   if (!finalized_) throw std::runtime_error("forward before finalize");
@@ -3366,6 +3448,7 @@ void Model<T, TS>::seg_tail(hipStream_t s, const float* sam_images, const int64_
                         const int32_t* ref_pos, int B, int Lmax, int teacher, const float* hidden, int hidden_rows,
                         const float* attn_mean, const int32_t* resized_hw, const int32_t* orig_hw, int32_t* out_nseg,
                         float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets, float* out_low) {
+  reports_begin(B);
   HIP_TRY(hipSetDevice(device_));
   const anyref_config& c = cfg;
   if (!finalized_) throw std::runtime_error("seg_tail before finalize");

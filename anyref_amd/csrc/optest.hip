@@ -5,6 +5,7 @@
 
 #include "../../include/anyref_hip_ops.h"
 #include "kernels.h"
+#include "mask_report.h"
 
 using namespace anyref;
 
@@ -386,6 +387,11 @@ int anyref_op_token_scores(void* stream, const float* logits, int M, int N, int 
     if (ldx < N) throw std::runtime_error("op_token_scores: ldx < N");
     launch_token_scores(logits, M, N, ldx, dst, logprob, gap, id, (hipStream_t)stream);
   });
+}
+
+int anyref_op_mask_report(void* stream, const float* logits, int n, int H, int W, float offset, int32_t* records,
+                          uint32_t* packed) {
+  OP_GUARD(launch_mask_report(logits, n, H, W, offset, records, packed, (hipStream_t)stream));
 }
 
 int anyref_op_draft_accept(void* stream, const float* logits, int B, int k, int N, int ldx, int64_t* p, const int64_t* draft,

@@ -69,7 +69,8 @@ _NEEDS_HANDLE = frozenset({
     "generate", "model_forward_new", "forward", "__call__", "encode_images", "sam_encode", "mask_decode", "llm_forward",
     "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
     "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session", "session_pool",
-    "set_rephrase_paths", "early_masks_done", "load_adapter", "set_adapter", "set_token_scores", "last_token_scores"})
+    "set_rephrase_paths", "early_masks_done", "load_adapter", "set_adapter", "set_token_scores", "last_token_scores",
+    "set_mask_reports", "last_mask_reports"})
 
 # the tensors an adapter's `modules_to_save` may carry (train.py:375-387) and anyref_update_weight replaces on a live handle
 _SAVED_EXACT = ("model.embed_tokens.weight", "lm_head.weight", "model.text_hidden_fcs.0.0.weight",
@@ -138,6 +139,10 @@ class AnyRefForCausalLM:
         self._scores_on = False                      # set_token_scores
         self._scores_call = None                     # (rows, max_new_tokens) of the last generating call, read on demand
         self._scores_many = None                     # generate_many: the entries of its calls, in the caller's item order
+        self._reports_on = False                     # set_mask_reports
+        self._reports_packed = False                 # ... with a packed-mask buffer armed for every mask-producing call
+        self._reports_call = None                    # (heights, widths, packed buffer) of the last such call, read on demand
+        self._reports_many = None                    # generate_many: the entries of its calls, in the caller's item order
         # `from_pretrained` flow: weights are gathered on the host first (base checkpoint, CLIP tower, SAM file,
         # token-row resize, LoRA merge all happen BEFORE `.cuda()` in the callers) and go to HBM in one build
         self._host_sd: Optional[Dict[str, torch.Tensor]] = {} if defer else None
@@ -584,6 +589,71 @@ class AnyRefForCausalLM:
             return list(self._scores_many)
         return self._read_token_scores()
 
+    # ---- mask reports (anyref_set_mask_reports) ----------------------------------------------------
+    def set_mask_reports(self, on: bool, offset: float = 1.0, packed: bool = False):
+        """What a caller wants to know about a mask without copying its f32 plane out (default off): with it
+        on, every mask of `generate`, `forward`, `seg_tail`, `ImageSession.generate`, `SessionPool.generate` /
+        `generate_many` is read once more on the device and leaves its area, its bounding box, SAM's stability score at
+        `offset`, and a count of non-finite logits (`last_mask_reports`).  `packed=True` also keeps the binary mask, 32 pixels
+        to a word, on the device: every such call then allocates sum_b max_seg * H_b * ceil(W_b / 32) words for it.  Off:
+        nothing is launched or allocated.  What the calls return is the same either way."""
+        self._check(self.lib.anyref_set_mask_reports(self.h, int(bool(on)), float(offset)), "set_mask_reports")
+        self._reports_on = bool(on)
+        self._reports_packed = bool(on) and bool(packed)
+        self._reports_call = self._reports_many = None
+
+    def _masks_begin(self, heights, widths):
+        """every mask-producing call, right before the library is entered: the reports of the call before are gone, and with
+        `packed` the buffer for this call's packed masks is armed (one-shot: the library takes it at its entry)"""
+        self._reports_call = self._reports_many = None
+        if not self._reports_on:
+            return None
+        buf = None
+        if self._reports_packed:
+            from .maskreport import packed_width
+            words = sum(self.max_seg * int(h) * packed_width(w) for h, w in zip(heights, widths))
+            buf = torch.empty(max(words, 1), device=self.device, dtype=torch.int32)
+            self._check(self.lib.anyref_set_packed_masks(self.h, _ptr(buf), words), "set_packed_masks")
+        return [int(h) for h in heights], [int(w) for w in widths], buf
+
+    def _masks_made(self, pending):
+        """... and after it returned: whose reports `last_mask_reports` reads"""
+        self._reports_call = pending
+
+    def _read_mask_reports(self):
+        from .maskreport import packed_width, stability
+        if self._reports_call is None:
+            return []
+        heights, widths, buf = self._reports_call
+        B, cap = len(heights), max(self.max_seg, 1)
+        n = torch.zeros(B, dtype=torch.int32)
+        rec = torch.zeros(B, cap, 8, dtype=torch.int32)
+        po = torch.zeros(B, dtype=torch.long)
+        self._check(self.lib.anyref_mask_reports(self.h, B, cap, _ptr(n), _ptr(rec), _ptr(po)), "mask_reports")
+        out = []
+        for b in range(B):
+            k = int(n[b])
+            r = rec[b, :k].to(torch.long)
+            words = heights[b] * packed_width(widths[b])
+            out.append(dict(
+                area=r[:, 0].clone(), area_hi=r[:, 1].clone(), area_lo=r[:, 2].clone(), nonfinite=r[:, 3].clone(),
+                box=r[:, 4:8].clone(), stability=torch.from_numpy(stability(rec[b, :k].numpy())),
+                packed=None if buf is None else buf[int(po[b]): int(po[b]) + k * words].view(k, heights[b], packed_width(widths[b]))))
+        return out
+
+    def last_mask_reports(self):
+        """One entry per row of the last `generate`, `forward`, `seg_tail`, `ImageSession.generate`, `SessionPool.generate` or
+        `generate_many` call (there: per item, in the caller's item order), for the n_b masks the library produced for the row
+        (its `out_nseg`): a dict of `area`, `area_hi`, `area_lo`, `nonfinite` (int64 [n_b]), `box` (int64 [n_b, 4]: inclusive
+        x0, y0, x1, y1; zeros for an empty mask), `stability` (f32 [n_b], NaN where area_lo is 0), all on the CPU, and
+        `packed`: an int32 [n_b, H, ceil(W / 32)] view of that call's device buffer (`maskreport.unpack` / `maskreport.rle`
+        read it), or None without `packed=True`.  The rule: anyref_amd/maskreport.py.  RuntimeError while the switch is off."""
+        if not self._reports_on:
+            raise RuntimeError("last_mask_reports: mask reports are off (model.set_mask_reports(True) before the call)")
+        if self._reports_many is not None:
+            return list(self._reports_many)
+        return self._read_mask_reports()
+
     # ---- per-kernel timing for bench.py ------------------------------------------------------
     def profile_enable(self, on: bool, only_tag: Optional[str] = None, sample_every: int = 1):
         self._check(self.lib.anyref_profile_config(self.h, only_tag.encode() if only_tag else None, sample_every),
@@ -876,9 +946,11 @@ class AnyRefForCausalLM:
         offs = torch.zeros(B, dtype=torch.long)
         cap = sum(self.max_seg * h * w for h, w in zip(height, width))
         out_masks = torch.empty(cap, device=self.device, dtype=torch.float32)
+        pending = self._masks_begin(height, width)
         self._check(self.lib.anyref_seg_tail(self.h, self._stream(), _ptr(sam), _ptr(ids), _ptr(lens), _ptr(rp), B, Lmax,
                                              int(teacher), _ptr(hid), hid.shape[1], _ptr(att), _ptr(rs), _ptr(os_),
                                              _ptr(nseg), _ptr(out_masks), cap, _ptr(offs), None), "seg_tail")
+        self._masks_made(pending)
         if int(nseg.sum()) == 0:
             return None, nseg
         return [out_masks[int(offs[b]): int(offs[b]) + int(nseg[b]) * height[b] * width[b]].view(int(nseg[b]), height[b], width[b])
@@ -928,11 +1000,13 @@ class AnyRefForCausalLM:
         eos = self.config.eos_token_id if self.config.eos_token_id is not None else -1
         if drafts is not None and any(drafts):
             self.set_draft(drafts)
+        pending = self._masks_begin(height, width)
         self._check(self.lib.anyref_generate(
             self.h, self._stream(), _ptr(clip), _ptr(sam), _ptr(ids), _ptr(lens), B, Lmax, _ptr(extra),
             _ptr(slots), n_extra, _ptr(rs), _ptr(os_), int(max_new_tokens), int(eos), _ptr(out_ids), _ptr(out_lens),
             _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)), "generate")
         self._generated(B, max_new_tokens)
+        self._masks_made(pending)
         if self._draft_policy == "last":
             self._last_answers = [out_ids[b, int(lens[b]): int(out_lens[b])].tolist() for b in range(B)]
         res = self._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width)
@@ -1046,10 +1120,12 @@ class AnyRefForCausalLM:
         logits = torch.empty(B, Sp, self.cfg.llm.vocab, device=self.device, dtype=torch.float32)
         hid = torch.empty(B, self.cfg.llm.max_seq, self.cfg.llm.dim, device=self.device,
                           dtype=torch.float32) if _return_extras else None
+        pending = self._masks_begin(height, width)
         self._check(self.lib.anyref_forward_teacher(
             self.h, self._stream(), _ptr(clip), _ptr(sam), _ptr(ids), _ptr(lens), B, Lmax, _ptr(extra), _ptr(slots),
             n_extra, _ptr(reph), _ptr(rs), _ptr(os_), _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), None,
             _ptr(hid), _ptr(logits)), "forward_teacher")
+        self._masks_made(pending)
         # LM loss (HF shift-by-one CE; the image span carries IGNORE labels)
         num, den = torch.zeros((), device=self.device), 0
         for b in range(B):
@@ -1193,11 +1269,13 @@ class ImageSession:
             drafts = normalize_drafts(draft_ids, Q)
             if any(drafts):
                 m.set_draft(drafts)
+        pending = m._masks_begin([self.height] * Q, [self.width] * Q)
         m._check(m.lib.anyref_session_generate(
             m.h, m._stream(), _ptr(suf), _ptr(slens), Q, Lmax, _ptr(extra), _ptr(slots), n_extra, int(max_new_tokens), int(eos),
             _ptr(out_ids), _ptr(out_lens), _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)),
             "session_generate")
         m._generated(Q, max_new_tokens)
+        m._masks_made(pending)
         res = m._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width, per_row=True)
         if _return_extras:
             return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **m.draft_stats(Q))
@@ -1360,11 +1438,13 @@ class SessionPool:
             drafts = normalize_drafts(draft_ids, Q)
             if any(drafts):
                 m.set_draft(drafts)
+        pending = m._masks_begin(height, width)
         m._check(m.lib.anyref_session_generate_pooled(
             m.h, m._stream(), _ptr(slots), _ptr(suf), _ptr(slens), Q, Lmax, _ptr(extra), _ptr(eslots), n_extra,
             int(max_new_tokens), int(eos), _ptr(out_ids), _ptr(out_lens), _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs),
             _ptr(out_low), _ptr(hid)), "session_generate_pooled")
         m._generated(Q, max_new_tokens)
+        m._masks_made(pending)
         for b, ps in enumerate(sessions):
             self.table.touch(ps.key)
             self._held[b] = (ps.slot, ps.gen)
@@ -1387,6 +1467,7 @@ class SessionPool:
             ps.check()
         out = [None] * len(items)
         scores = [None] * len(items) if self.model._scores_on else None
+        reports = [None] * len(items) if self.model._reports_on else None
         for order in plan_calls([(ps.slot, ps.gen) for ps, _ in items], self.model.max_batch, self._held):
             rows = [items[i][1] for i in order]
             n = max(len(r) for r in rows)
@@ -1400,6 +1481,9 @@ class SessionPool:
             if scores is not None:                # (the next call clears them)
                 for b, e in enumerate(self.model._read_token_scores()):
                     scores[order[b]] = e
+            if reports is not None:
+                for b, e in enumerate(self.model._read_mask_reports()):
+                    reports[order[b]] = e
             for b, i in enumerate(order):
                 n_ids, nseg = int(ex["out_lens"][b]), int(ex["nseg"][b])
                 one = (res[0][b, :n_ids], res[1][b] if res[1] is not None and nseg > 0 else None)
@@ -1407,6 +1491,7 @@ class SessionPool:
                     one += (dict(low_res=ex["low_res"][b], nseg=nseg, hidden=None if ex["hidden"] is None else ex["hidden"][b]),)
                 out[i] = one
         self.model._scores_many = scores
+        self.model._reports_many = reports
         return out
 
 

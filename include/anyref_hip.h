@@ -300,6 +300,31 @@ int anyref_set_token_scores(anyref_handle* h, int on);
  * and if a row holds more than n_cap tokens. */
 int anyref_token_scores(anyref_handle* h, int B, int n_cap, float* logprob, float* gap, int32_t* n);
 
+/* Mask reports: what a caller wants to know about every mask without copying its f32 plane out.  Off by
+ * default; while off nothing is launched or allocated for it and every call queues exactly what it queued before.  On: every
+ * mask that anyref_generate, anyref_forward_teacher, anyref_seg_tail, anyref_session_generate and
+ * anyref_session_generate_pooled write to out_masks is read once more on the device, right behind the kernel that wrote it
+ * (mask_report_kernel; anyref_op_mask_report states the rule, anyref_amd/maskreport.py holds it), and leaves an i32 record
+ *   {area #{x > 0}, area_hi #{x > offset}, area_lo #{x > -offset}, nonfinite #{NaN, +-inf}, x0, y0, x1, y1}
+ * with the inclusive box of the bits x > 0 (0, 0, 0, 0 for an empty mask).  area_hi / area_lo is SAM's stability score.
+ * `offset` must be finite and >= 0 (SAM's default is 1.0).  The first switch-on allocates the device records
+ * [max_batch, max_seg, 8].  Exact integer arithmetic: the records of a call depend on its out_masks alone.  The decode step's
+ * graphs do not depend on the switch: no report is launched inside them. */
+int anyref_set_mask_reports(anyref_handle* h, int on, float offset);
+/* A caller-owned device buffer of cap_words u32 words for the bit-packed masks of the NEXT mask-producing call (the five
+ * above) -- one-shot, like anyref_set_draft: taken and cleared at the entry of that call, used or not, and nothing stays
+ * armed after an error; NULL cancels.  Needs the switch above on at that call.  Mask j of row b, H_b x W_b, takes H_b * Wp_b
+ * words, Wp_b = ceil(W_b / 32), from word pack_offsets[b] + j * H_b * Wp_b, rows in order (pack_offsets mirrors mask_offsets:
+ * anyref_mask_reports returns it): bit k (LSB first) of word w of row y is x[y, 32 w + k] > 0, bits past W_b are 0.  A
+ * capacity too small for the call's masks is refused where a too small out_masks_cap is. */
+int anyref_set_packed_masks(anyref_handle* h, uint32_t* packed_dev, int64_t cap_words);
+/* Of the last mask-producing call, for its rows b < B: n[b] = masks of row b (its out_nseg), their records at
+ * rec[(b * seg_cap + j) * 8 ..] (i32 host, [B, seg_cap, 8]; entries past n[b] are left alone) and, if pack_offsets is not
+ * NULL, pack_offsets[b] (i64 host [B]; meaningful when that call had a packed buffer armed).  Waits for that call's
+ * stream to have produced them.  Every mask-producing call clears this state on entry; rows the call did not have report
+ * n = 0.  Error while the switch is off, and if a row holds more than seg_cap masks. */
+int anyref_mask_reports(anyref_handle* h, int B, int seg_cap, int32_t* n, int32_t* rec, int64_t* pack_offsets);
+
 /*
  * Image sessions: the callers' loops ask several questions about one image (RefCOCO: ~7 expressions per image,
  * one `generate` each with the same clip_images / sam_images, eval_referseg.py:124-137).  Everything that depends only on the

@@ -74,6 +74,15 @@ int anyref_op_argmax(void* stream, const float* x, int M, int N, int ldx, int64_
  * logprob = gap = NaN; -inf entries add 0 to the sum.  Error (nothing launched) if M < 1, N < 2 or ldx < N. */
 int anyref_op_token_scores(void* stream, const float* logits, int M, int N, int ldx, const int32_t* dst, float* logprob,
                            float* gap, int64_t* id);
+/* mask report (anyref_set_mask_reports; the rule: anyref_amd/maskreport.py) of mask logits f32 [n, H, W] (contiguous, any 4-byte
+ * alignment) with stability offset d = `offset` >= 0.  records i32 [n, 8] = {area #{x > 0}, area_hi #{x > d}, area_lo #{x > -d},
+ * nonfinite #{NaN, +-inf}, x0, y0, x1, y1} -- the inclusive box of the bits x > 0, all 0 for an empty mask.  packed u32
+ * [n, H, Wp], Wp = ceil(W / 32), or NULL: bit k (LSB first) of word w of row y is x[y, 32 w + k] > 0, bits past W are 0.  NaN and
+ * -0.0 give bit 0.  The records need no clearing by the caller.  Exact: integer counts, bit-identical on a rerun.  Error (nothing
+ * queued) if H < 1, W < 1, H * W > INT32_MAX, n > 65535, the offset is negative or not finite, or logits / records is NULL;
+ * n <= 0 does nothing. */
+int anyref_op_mask_report(void* stream, const float* logits, int n, int H, int W, float offset, int32_t* records,
+                          uint32_t* packed);
 /* accept step of the draft-verified greedy decode (anyref_set_draft): logits f32 [B * k, N] (row stride ldx) of a verification
  * pass that fed draft i64 [B, k] (draft_lens[b] <= k valid ids per row, 0 = none) behind next[b], the token already chosen.
  * p i64 [B * k] receives the row argmaxes (first index on ties).  Per row, with g[0] = next[b], g[j + 1] = p[j]: accepted[b] = m =
