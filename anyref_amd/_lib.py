@@ -77,6 +77,13 @@ class AttnEx(C.Structure):
                                           "max_wg")] +
                 [("scale", _F)])
 
+
+class SpatialPrompts(C.Structure):
+    """anyref_spatial_prompts (include/anyref_hip.h)"""
+    _fields_ = [("points", _P), ("labels", _P), ("n_points", C.c_int32), ("boxes", _P), ("mask_input", _P),
+                ("multimask", C.c_int32)]
+
+
 class LoraPair(C.Structure):
     """anyref_lora_pair (include/anyref_hip.h)"""
     _fields_ = [("weight_name", C.c_char_p), ("A", _P), ("B", _P), ("r", C.c_int32), ("is_device", C.c_int32),
@@ -100,6 +107,10 @@ SYMBOLS = {
     "anyref_encode_images": (_I, [_P, _P, _P, _I, _P, _P]),
     "anyref_sam_encode": (_I, [_P, _P, _P, _I, _P]),
     "anyref_mask_decode": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "anyref_prompt_reserve": (_I, [_P, _I]),
+    "anyref_mask_decode_prompted": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "anyref_refine_masks": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "anyref_refine_embedding": (_I, [_P, _P, _I, _I, _P]),
     "anyref_llm_forward": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "anyref_llm_extend": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "anyref_set_draft": (_I, [_P, _P, _P, _I, _I]),
@@ -197,6 +208,8 @@ SYMBOLS = {
     "anyref_op_upscale2_masks": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "anyref_op_dense_pe": (_I, [_P, _P, _I, _I, _P]),
     "anyref_op_build_tokens": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "anyref_op_prompt_tokens": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I]),
+    "anyref_op_mask_prompt_embed": (_I, [_P] * 13 + [_I, _I, _I, _I, _I, _P, _I]),
     "anyref_op_add_rows": (_I, [_P, _P, _P, _I, _P, _I, _I]),
     "anyref_op_add_vec": (_I, [_P, _P, _P, _P, _I, _I]),
     "anyref_op_embed_splice": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _I, _I, _P]),

@@ -66,7 +66,7 @@ int anyref_set_weight(anyref_handle* h, const char* name, const void* ptr, int i
   GUARD(h, h->m->set_weight(name, ptr, is_device, dtype, shape, ndim));
 }
 
-int anyref_finalize(anyref_handle* h) { GUARD(h, h->m->end_session("anyref_finalize"); h->m->end_slots("anyref_finalize"); h->m->finalize()); }
+int anyref_finalize(anyref_handle* h) { GUARD(h, h->m->end_session("anyref_finalize"); h->m->end_slots("anyref_finalize"); h->m->refine_forget("anyref_finalize"); h->m->finalize()); }
 
 int anyref_generate(anyref_handle* h, void* stream, const float* clip_images, const float* sam_images,
                     const int64_t* input_ids, const int32_t* lens, int B, int Lmax, const float* extra_embeds,
@@ -74,7 +74,7 @@ int anyref_generate(anyref_handle* h, void* stream, const float* clip_images, co
                     int max_new_tokens, int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg,
                     float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets, float* out_low,
                     float* out_hidden) {
-  GUARD(h, h->m->end_session("anyref_generate"); h->m->generate((hipStream_t)stream, clip_images, sam_images, input_ids, lens, B, Lmax, extra_embeds,
+  GUARD(h, h->m->end_session("anyref_generate"); h->m->refine_begin("anyref_generate"); h->m->generate((hipStream_t)stream, clip_images, sam_images, input_ids, lens, B, Lmax, extra_embeds,
                           extra_slots, n_extra, resized_hw, orig_hw, max_new_tokens, eos_token_id, out_ids,
                           out_lens, out_nseg, out_masks, out_masks_cap, mask_offsets, out_low, out_hidden));
 }
@@ -85,7 +85,7 @@ int anyref_forward_teacher(anyref_handle* h, void* stream, const float* clip_ima
                            const int32_t* rephrase_start, const int32_t* resized_hw, const int32_t* orig_hw,
                            int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
                            float* out_low, float* out_hidden, float* out_logits) {
-  GUARD(h, h->m->end_session("anyref_forward_teacher"); h->m->forward_teacher((hipStream_t)stream, clip_images, sam_images, input_ids, lens, B, Lmax,
+  GUARD(h, h->m->end_session("anyref_forward_teacher"); h->m->refine_forget("anyref_forward_teacher"); h->m->forward_teacher((hipStream_t)stream, clip_images, sam_images, input_ids, lens, B, Lmax,
                                  extra_embeds, extra_slots, n_extra, rephrase_start, resized_hw, orig_hw, out_nseg,
                                  out_masks, out_masks_cap, mask_offsets, out_low, out_hidden, out_logits));
 }
@@ -96,13 +96,30 @@ int anyref_encode_images(anyref_handle* h, void* stream, const float* clip_image
 }
 
 int anyref_sam_encode(anyref_handle* h, void* stream, const float* sam_images, int B, float* out) {
-  GUARD(h, h->m->sam_encode((hipStream_t)stream, sam_images, B, out));
+  GUARD(h, h->m->refine_forget("anyref_sam_encode"); h->m->sam_encode((hipStream_t)stream, sam_images, B, out));
 }
 
 int anyref_mask_decode(anyref_handle* h, void* stream, const float* image_emb, const float* pred_emb, int n,
                        float* masks4, float* iou, const int32_t* resized_hw, const int32_t* orig_hw,
                        float* out_masks) {
   GUARD(h, h->m->mask_decode((hipStream_t)stream, image_emb, pred_emb, n, masks4, iou, resized_hw, orig_hw, out_masks));
+}
+
+int anyref_prompt_reserve(anyref_handle* h, int max_points) { GUARD(h, h->m->prompt_reserve(max_points)); }
+
+int anyref_mask_decode_prompted(anyref_handle* h, void* stream, const float* image_emb, const float* pred_emb, int n,
+                                const anyref_spatial_prompts* sp, float* masks4, float* iou, const int32_t* resized_hw,
+                                const int32_t* orig_hw, float* out_masks) {
+  GUARD(h, h->m->mask_decode_prompted((hipStream_t)stream, image_emb, pred_emb, n, sp, masks4, iou, resized_hw, orig_hw, out_masks));
+}
+
+int anyref_refine_masks(anyref_handle* h, void* stream, int row, int seg, const anyref_spatial_prompts* sp, float* out_low,
+                        float* iou, float* out_masks) {
+  GUARD(h, h->m->refine_masks((hipStream_t)stream, row, seg, sp, out_low, iou, out_masks));
+}
+
+int anyref_refine_embedding(anyref_handle* h, void* stream, int row, int seg, float* out) {
+  GUARD(h, h->m->refine_embedding((hipStream_t)stream, row, seg, out));
 }
 
 int anyref_llm_forward(anyref_handle* h, void* stream, const float* embeds, const int32_t* lens, int B, int S,
@@ -117,14 +134,14 @@ int anyref_llm_extend(anyref_handle* h, void* stream, const float* embeds, const
 
 int anyref_session_open(anyref_handle* h, void* stream, const float* clip_image, const float* sam_image,
                         const int64_t* prefix_ids, int prefix_len, const int32_t* resized_hw, const int32_t* orig_hw) {
-  GUARD(h, h->m->session_open((hipStream_t)stream, clip_image, sam_image, prefix_ids, prefix_len, resized_hw, orig_hw));
+  GUARD(h, h->m->refine_forget("anyref_session_open"); h->m->session_open((hipStream_t)stream, clip_image, sam_image, prefix_ids, prefix_len, resized_hw, orig_hw));
 }
 
 int anyref_session_generate(anyref_handle* h, void* stream, const int64_t* suffix_ids, const int32_t* lens, int Q, int Lmax,
                             const float* extra_embeds, const int32_t* extra_slots, int n_extra, int max_new_tokens,
                             int eos_token_id, int64_t* out_ids, int32_t* out_lens, int32_t* out_nseg, float* out_masks,
                             int64_t out_masks_cap, int64_t* mask_offsets, float* out_low, float* out_hidden) {
-  GUARD(h, h->m->session_generate((hipStream_t)stream, suffix_ids, lens, Q, Lmax, extra_embeds, extra_slots, n_extra,
+  GUARD(h, h->m->refine_begin("anyref_session_generate"); h->m->session_generate((hipStream_t)stream, suffix_ids, lens, Q, Lmax, extra_embeds, extra_slots, n_extra,
                                   max_new_tokens, eos_token_id, out_ids, out_lens, out_nseg, out_masks, out_masks_cap,
                                   mask_offsets, out_low, out_hidden));
 }
@@ -142,7 +159,7 @@ int anyref_session_generate_pooled(anyref_handle* h, void* stream, const int32_t
                                    int n_extra, int max_new_tokens, int eos_token_id, int64_t* out_ids, int32_t* out_lens,
                                    int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets,
                                    float* out_low, float* out_hidden) {
-  GUARD(h, h->m->session_generate_pooled((hipStream_t)stream, slots, suffix_ids, lens, Q, Lmax, extra_embeds, extra_slots, n_extra,
+  GUARD(h, h->m->refine_begin("anyref_session_generate_pooled"); h->m->session_generate_pooled((hipStream_t)stream, slots, suffix_ids, lens, Q, Lmax, extra_embeds, extra_slots, n_extra,
                                          max_new_tokens, eos_token_id, out_ids, out_lens, out_nseg, out_masks, out_masks_cap,
                                          mask_offsets, out_low, out_hidden));
 }
@@ -207,7 +224,7 @@ int anyref_seg_tail(anyref_handle* h, void* stream, const float* sam_images, con
                     const int32_t* ids_lens, const int32_t* ref_pos, int B, int Lmax, int teacher, const float* hidden,
                     int hidden_rows, const float* attn_mean, const int32_t* resized_hw, const int32_t* orig_hw,
                     int32_t* out_nseg, float* out_masks, int64_t out_masks_cap, int64_t* mask_offsets, float* out_low) {
-  GUARD(h, h->m->end_session("anyref_seg_tail"); h->m->seg_tail((hipStream_t)stream, sam_images, ids, ids_lens, ref_pos, B, Lmax, teacher, hidden,
+  GUARD(h, h->m->end_session("anyref_seg_tail"); h->m->refine_forget("anyref_seg_tail"); h->m->seg_tail((hipStream_t)stream, sam_images, ids, ids_lens, ref_pos, B, Lmax, teacher, hidden,
                           hidden_rows, attn_mean, resized_hw, orig_hw, out_nseg, out_masks, out_masks_cap,
                           mask_offsets, out_low));
 }

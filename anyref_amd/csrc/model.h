@@ -8,6 +8,7 @@
 
 #include "../../include/anyref_hip.h"
 #include "kernels.h"
+#include "prompt_encode.h"
 
 namespace anyref {
 
@@ -48,6 +49,33 @@ class ModelBase {
   virtual void sam_encode(hipStream_t s, const float* sam_images, int B, float* out) = 0;
   virtual void mask_decode(hipStream_t s, const float* image_emb, const float* pred_emb, int n, float* masks4,
                            float* iou, const int32_t* resized_hw, const int32_t* orig_hw, float* out_masks) = 0;
+  // ---- SAM spatial prompts beside [SEG] (anyref_prompt_reserve / _mask_decode_prompted / _refine_masks) ----
+  virtual void prompt_reserve(int max_points) = 0;
+  virtual void mask_decode_prompted(hipStream_t s, const float* image_emb, const float* pred_emb, int n,
+                                    const anyref_spatial_prompts* sp, float* masks4, float* iou, const int32_t* resized_hw,
+                                    const int32_t* orig_hw, float* out_masks) = 0;
+  virtual void refine_masks(hipStream_t s, int row, int seg, const anyref_spatial_prompts* sp, float* out_low, float* iou,
+                            float* out_masks) = 0;
+  virtual void refine_embedding(hipStream_t s, int row, int seg, float* out) = 0;
+  // where mask (row, seg) of the last generating call came from: rows [pred_row0, pred_row0 + n) of the prompt embeddings,
+  // image-embedding slot emb_slot, and the row's sizes
+  struct RefineRow {
+    int pred_row0 = 0, n = 0, emb_slot = 0;
+    int32_t rhw[2] = {0, 0}, ohw[2] = {0, 0};
+  };
+  std::vector<RefineRow> refine_rows_;
+  const char* refine_lost_by_ = nullptr;  // entry that overwrote what a refine reads (for the error text)
+  bool refine_arm_ = false;               // the running call is a generating one: run_tail records its rows
+  // every entry that writes the image embeddings or the prompt embeddings calls one of the two first (api.hip)
+  void refine_forget(const char* by) {
+    if (!refine_rows_.empty()) refine_lost_by_ = by;
+    refine_rows_.clear();
+    refine_arm_ = false;
+  }
+  void refine_begin(const char* by) {
+    refine_forget(by);
+    refine_arm_ = true;
+  }
   virtual void llm_forward(hipStream_t s, const float* embeds, const int32_t* lens, int B, int S, float* hidden,
                            float* logits, const int32_t* attn_q, float* attn_row) = 0;
   virtual void llm_extend(hipStream_t s, const float* embeds, const int32_t* pos0, const int32_t* lens, int B, int n,

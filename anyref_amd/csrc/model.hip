@@ -357,6 +357,14 @@ class Model : public ModelBase {
   void sam_encode(hipStream_t s, const float* sam_images, int B, float* out) override;
   void mask_decode(hipStream_t s, const float* image_emb, const float* pred_emb, int n, float* masks4, float* iou,
                    const int32_t* resized_hw, const int32_t* orig_hw, float* out_masks) override;
+  void prompt_reserve(int max_points) override;
+  void mask_decode_prompted(hipStream_t s, const float* image_emb, const float* pred_emb, int n, const anyref_spatial_prompts* sp,
+                            float* masks4, float* iou, const int32_t* resized_hw, const int32_t* orig_hw, float* out_masks) override;
+  void refine_masks(hipStream_t s, int row, int seg, const anyref_spatial_prompts* sp, float* out_low, float* iou,
+                    float* out_masks) override;
+  void refine_embedding(hipStream_t s, int row, int seg, float* out) override;
+  const RefineRow& refine_row(const char* who, int row, int seg) const;
+  void check_prompts(const char* who, const anyref_spatial_prompts* sp) const;
   void llm_forward(hipStream_t s, const float* embeds, const int32_t* lens, int B, int S, float* hidden,
                    float* logits, const int32_t* attn_q, float* attn_row) override;
   void llm_extend(hipStream_t s, const float* embeds, const int32_t* pos0, const int32_t* lens, int B, int n, float* hidden,
@@ -657,7 +665,7 @@ class Model : public ModelBase {
   // blocks [blk0, blk1) of the encoder; blk0 == 0 also runs the patch embedding, blk1 < 0 (= to the end) the neck
   void sam_encoder(hipStream_t s, const float* images, int B, float* out, int blk0 = 0, int blk1 = -1);
   void mask_decoder(hipStream_t s, const float* image_emb, const float* pred_emb, int n, float* masks4,
-                    float* iou);
+                    float* iou, const anyref_spatial_prompts* sp = nullptr);
   void run_tail(hipStream_t s, const float* sam_images, int B, const std::vector<int>& seg_b,
                 const std::vector<int>& seg_pos, const std::vector<int>& reph_s, const int32_t* resized_hw,
                 const int32_t* orig_hw, int32_t* out_nseg, float* out_masks, int64_t out_masks_cap,
@@ -876,8 +884,20 @@ class Model : public ModelBase {
   Affine dec_norm_final_, up_ln_;
   LinF up1_, up2_;
   LinF hyper_[3], iou_head_[3];  // hyper: stacked over the mask tokens
-  float *m_tokens_ = nullptr, *m_q_ = nullptr, *m_qp_ = nullptr, *m_keys_ = nullptr, *m_kp_ = nullptr,
-        *m_qh_ = nullptr, *m_kh_ = nullptr, *m_vh_ = nullptr, *m_att_ = nullptr, *m_tmp_ = nullptr, *m_mlp_ = nullptr,
+  // the decoder's token-side workspaces, [n, NQ, *]: dq_ for the text prompt alone (NQ = nt + 2), pq_ for the prompted
+  // path (NQ up to nt + 1 + max_points + 2 + 1; anyref_prompt_reserve)
+  struct DecQ {
+    float *tokens = nullptr, *q = nullptr, *qp = nullptr, *qh = nullptr, *kh = nullptr, *vh = nullptr, *att = nullptr,
+          *mlp = nullptr;
+  };
+  DecQ dq_, pq_;
+  // ---- spatial prompts (anyref_prompt_reserve / anyref_mask_decode_prompted / anyref_refine_masks) ----
+  float *sp_gauss_ = nullptr, *sp_emb5_ = nullptr;  // kept by finalize only when the point embeddings were handed over
+  MaskDownW sp_md_;
+  std::string sp_missing_;  // first spatial tensor finalize did not find ("" = all there)
+  int sp_maxP_ = 0;         // 0: nothing reserved
+  void prompt_setup();      // finalize: take the spatial weights if they are there
+  float *m_keys_ = nullptr, *m_kp_ = nullptr, *m_tmp_ = nullptr,
         *m_bigq_ = nullptr, *m_bigk_ = nullptr, *m_bigv_ = nullptr, *m_bigatt_ = nullptr, *m_up0_ = nullptr,
         *m_up1_ = nullptr, *m_up2_ = nullptr, *m_hy0_ = nullptr, *m_hy1_ = nullptr, *m_hyper_ = nullptr,
         *m_masks_ = nullptr, *m_iou_ = nullptr, *m_src_ = nullptr;
@@ -1371,15 +1391,16 @@ void Model<T, TS>::finalize() {
       iou_head_[j] = pack_linear_f32(ip + ".weight", ip + ".bias", idims[j + 1], idims[j]);
     }
     const int n = c.max_seg, NQ = nt + 2;
-    m_tokens_ = talloc<float>((size_t)n * NQ * C);
-    m_q_ = talloc<float>((size_t)n * NQ * C);
-    m_qp_ = talloc<float>((size_t)n * NQ * C);
-    m_qh_ = talloc<float>((size_t)n * NQ * C);
-    m_kh_ = talloc<float>((size_t)n * NQ * C);
-    m_vh_ = talloc<float>((size_t)n * NQ * C);
-    m_att_ = talloc<float>((size_t)n * NQ * C);
-    m_tmp_ = talloc<float>((size_t)n * NQ * C);
-    m_mlp_ = talloc<float>((size_t)n * NQ * c.dec_mlp);
+    DecQ& W = dq_;
+    W.tokens = talloc<float>((size_t)n * NQ * C);
+    W.q = talloc<float>((size_t)n * NQ * C);
+    W.qp = talloc<float>((size_t)n * NQ * C);
+    W.qh = talloc<float>((size_t)n * NQ * C);
+    W.kh = talloc<float>((size_t)n * NQ * C);
+    W.vh = talloc<float>((size_t)n * NQ * C);
+    W.att = talloc<float>((size_t)n * NQ * C);
+    m_tmp_ = talloc<float>((size_t)n * NQ * C);  // read by nothing any more: kept so that a handle holds the bytes it always held
+    W.mlp = talloc<float>((size_t)n * NQ * c.dec_mlp);
     m_src_ = talloc<float>((size_t)NK * C);
     m_keys_ = talloc<float>((size_t)n * NK * C);
     m_kp_ = talloc<float>((size_t)n * NK * C);
@@ -1395,6 +1416,7 @@ void Model<T, TS>::finalize() {
     m_hyper_ = talloc<float>((size_t)n * nt * (C / 8));
     m_masks_ = talloc<float>((size_t)n * nt * 16 * NK);
     m_iou_ = talloc<float>((size_t)n * nt);
+    prompt_setup();
   }
   // ================= ImageBind audio trunk =================
   if (c.aud_blocks > 0) {
@@ -2362,20 +2384,101 @@ void Model<T, TS>::sam_encode(hipStream_t s, const float* sam_images, int B, flo
 }
 
 // ---------------------------------------------------------------------------------------------
-// prompt encoder (text) + mask decoder, all f32
+// spatial prompts: the optional half of the prompt encoder (prompt_encoder.py:78-186)
+// ---------------------------------------------------------------------------------------------
+template <typename T, typename TS>
+void Model<T, TS>::prompt_setup() {
+  const std::string pp = std::string(SAM_P) + "prompt_encoder.";
+  const int C = cfg.sam_out_chans;
+  const char* names[] = {"point_embeddings.0.weight", "point_embeddings.1.weight", "point_embeddings.2.weight",
+                         "point_embeddings.3.weight", "not_a_point_embed.weight", "mask_downscaling.0.weight",
+                         "mask_downscaling.0.bias", "mask_downscaling.1.weight", "mask_downscaling.1.bias",
+                         "mask_downscaling.3.weight", "mask_downscaling.3.bias", "mask_downscaling.4.weight",
+                         "mask_downscaling.4.bias", "mask_downscaling.6.weight", "mask_downscaling.6.bias"};
+  sp_missing_.clear();
+  for (const char* nm : names)
+    if (!has_raw(pp + nm)) {  // optional: a handle without them is the handle it always was
+      sp_missing_ = pp + nm;
+      return;
+    }
+  const RawTensor &w1 = raw(pp + names[5]), &w2 = raw(pp + names[9]), &w3 = raw(pp + names[13]);
+  const int c1 = w1.shape.empty() ? 0 : (int)w1.shape[0], c2 = w2.shape.empty() ? 0 : (int)w2.shape[0];
+  if (c1 < 1 || c2 < 1 || w1.numel() != (int64_t)c1 * 4 || w2.numel() != (int64_t)c2 * c1 * 4 || w3.numel() != (int64_t)C * c2)
+    throw std::runtime_error("prompt_encoder.mask_downscaling: conv shapes must be [c1,1,2,2], [c2,c1,2,2], [C,c2,1,1]");
+  const int want[15] = {C, C, C, C, C, c1 * 4, c1, c1, c1, c2 * c1 * 4, c2, c2, c2, C * c2, C};
+  for (int i = 0; i < 15; ++i)
+    if (raw(pp + names[i]).numel() != want[i]) throw std::runtime_error(std::string("spatial prompt weight shape: ") + pp + names[i]);
+  // the five embeddings as one [5, C] table (the same bytes as the five tensors, which finalize then drops)
+  sp_emb5_ = talloc<float>((size_t)5 * C);
+  for (int i = 0; i < 5; ++i)
+    HIP_TRY(hipMemcpy(sp_emb5_ + (size_t)i * C, raw(pp + names[i]).p, (size_t)C * 4, hipMemcpyDeviceToDevice));
+  // the Gaussian matrix itself: dense_pe_ holds its sines only, a point needs the matrix (C floats more)
+  sp_gauss_ = talloc<float>((size_t)C);
+  HIP_TRY(hipMemcpy(sp_gauss_, raw(pp + "pe_layer.positional_encoding_gaussian_matrix").p, (size_t)C * 4, hipMemcpyDeviceToDevice));
+  sp_md_.c1 = c1;
+  sp_md_.c2 = c2;
+  sp_md_.w1 = own_f32(pp + names[5]);  sp_md_.b1 = own_f32(pp + names[6]);
+  sp_md_.g1 = own_f32(pp + names[7]);  sp_md_.be1 = own_f32(pp + names[8]);
+  sp_md_.w2 = own_f32(pp + names[9]);  sp_md_.b2 = own_f32(pp + names[10]);
+  sp_md_.g2 = own_f32(pp + names[11]); sp_md_.be2 = own_f32(pp + names[12]);
+  sp_md_.w3 = own_f32(pp + names[13]); sp_md_.b3 = own_f32(pp + names[14]);
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::prompt_reserve(int max_points) {
+  HIP_TRY(hipSetDevice(device_));
+  if (!finalized_) throw std::runtime_error("anyref_prompt_reserve before anyref_finalize");
+  if (max_points < 0) throw std::runtime_error("anyref_prompt_reserve: max_points < 0");
+  if (max_points > 0 && !sp_missing_.empty())
+    throw std::runtime_error("anyref_prompt_reserve: the spatial prompt weights were not handed over; missing weight: " + sp_missing_);
+  if (max_points == sp_maxP_) return;
+  HIP_TRY(hipDeviceSynchronize());  // nothing queued may still read what is freed below
+  for (float** p : {&pq_.tokens, &pq_.q, &pq_.qp, &pq_.qh, &pq_.kh, &pq_.vh, &pq_.att, &pq_.mlp}) {
+    if (*p) dfree(*p);
+    *p = nullptr;
+  }
+  sp_maxP_ = max_points;
+  refine_forget("anyref_prompt_reserve");
+  if (max_points == 0) return;
+  const anyref_config& c = cfg;
+  const size_t n = c.max_seg, NQ = c.num_mask_tokens + 1 + max_points + 2 + 1, C = c.sam_out_chans;
+  pq_.tokens = talloc<float>(n * NQ * C);
+  pq_.q = talloc<float>(n * NQ * C);
+  pq_.qp = talloc<float>(n * NQ * C);
+  pq_.qh = talloc<float>(n * NQ * C);
+  pq_.kh = talloc<float>(n * NQ * C);
+  pq_.vh = talloc<float>(n * NQ * C);
+  pq_.att = talloc<float>(n * NQ * C);
+  pq_.mlp = talloc<float>(n * NQ * c.dec_mlp);
+}
+
+// ---------------------------------------------------------------------------------------------
+// prompt encoder + mask decoder, all f32.  sp == nullptr: the text prompt alone, as generate runs it
 // ---------------------------------------------------------------------------------------------
 template <typename T, typename TS>
 void Model<T, TS>::mask_decoder(hipStream_t s, const float* image_emb, const float* pred_emb, int n, float* masks4,
-                            float* iou) {
+                            float* iou, const anyref_spatial_prompts* sp) {
   const anyref_config& c = cfg;
-  const int C = c.sam_out_chans, g = sam_g_, NK = g * g, nt = c.num_mask_tokens, NQ = nt + 2, Ci = C / 2;
+  const int C = c.sam_out_chans, g = sam_g_, NK = g * g, nt = c.num_mask_tokens, Ci = C / 2;
+  const int NQ = sp ? prompt_token_rows(nt + 1, sp->n_points, sp->boxes != nullptr, pred_emb != nullptr) : nt + 2;
   const int nh = c.dec_heads;
-  // tokens = [iou, mask x nt, text prompt]; src = image embedding + no_mask dense embedding
-  launch_build_tokens(out_tokens_, nt + 1, pred_emb, n, C, m_tokens_, s);
-  launch_add_vec(image_emb, no_mask_, m_src_, NK, C, s);
-  for (int i = 0; i < n; ++i)
-    HIP_TRY(hipMemcpyAsync(m_keys_ + (size_t)i * NK * C, m_src_, (size_t)NK * C * 4, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(m_q_, m_tokens_, (size_t)n * NQ * C * 4, hipMemcpyDeviceToDevice, s));
+  const DecQ& W = sp ? pq_ : dq_;
+  if (sp) {
+    // tokens = [iou, mask x nt, points, pad, box corners, text prompt]; src = image embedding + mask_downscaling or no_mask
+    launch_prompt_tokens(out_tokens_, nt + 1, sp->points, sp->labels, sp->n_points, sp->boxes, pred_emb, sp_gauss_, sp_emb5_, n, C,
+                         c.sam_img, W.tokens, s);
+  } else {
+    // tokens = [iou, mask x nt, text prompt]; src = image embedding + no_mask dense embedding
+    launch_build_tokens(out_tokens_, nt + 1, pred_emb, n, C, W.tokens, s);
+  }
+  if (sp && sp->mask_input) {
+    launch_mask_prompt_embed(sp->mask_input, image_emb, sp_md_, n, g, C, m_keys_, s);
+  } else {
+    launch_add_vec(image_emb, no_mask_, m_src_, NK, C, s);
+    for (int i = 0; i < n; ++i)
+      HIP_TRY(hipMemcpyAsync(m_keys_ + (size_t)i * NK * C, m_src_, (size_t)NK * C * 4, hipMemcpyDeviceToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(W.q, W.tokens, (size_t)n * NQ * C * 4, hipMemcpyDeviceToDevice, s));
 
   auto attn = [&](const float* Q, const float* K, const float* V, float* O, int Sq, int Sk, int internal) {
     AttnArgs a;
@@ -2394,51 +2497,51 @@ void Model<T, TS>::mask_decoder(hipStream_t s, const float* image_emb, const flo
   };
   // token -> image attention with weights `A`; queries += out
   auto token_to_image = [&](const DecAttn& A) {
-    launch_add_rows(m_q_, m_tokens_, n * NQ, m_qp_, n * NQ, C, s);   // q = queries + query_pe
+    launch_add_rows(W.q, W.tokens, n * NQ, W.qp, n * NQ, C, s);   // q = queries + query_pe
     launch_add_rows(m_keys_, dense_pe_, NK, m_kp_, n * NK, C, s);    // k = keys + key_pe
-    gemmf(s, m_qp_, C, A.q, m_qh_, Ci, n * NQ, ACT_NONE);
+    gemmf(s, W.qp, C, A.q, W.qh, Ci, n * NQ, ACT_NONE);
     gemmf(s, m_kp_, C, A.k, m_bigk_, Ci, n * NK, ACT_NONE);
     gemmf(s, m_keys_, C, A.v, m_bigv_, Ci, n * NK, ACT_NONE);
-    attn(m_qh_, m_bigk_, m_bigv_, m_att_, NQ, NK, Ci);
-    gemmf(s, m_att_, Ci, A.o, m_q_, C, n * NQ, ACT_NONE, m_q_, C);
+    attn(W.qh, m_bigk_, m_bigv_, W.att, NQ, NK, Ci);
+    gemmf(s, W.att, Ci, A.o, W.q, C, n * NQ, ACT_NONE, W.q, C);
   };
 
   for (int i = 0; i < c.dec_depth; ++i) {
     DecLayer& L = dec_layers_[i];
     // (1) self attention of the tokens (layer 0: no PE, output replaces the queries; transformer.py:153-160)
-    const float* qin = m_q_;
+    const float* qin = W.q;
     if (i > 0) {
-      launch_add_rows(m_q_, m_tokens_, n * NQ, m_qp_, n * NQ, C, s);
-      qin = m_qp_;
+      launch_add_rows(W.q, W.tokens, n * NQ, W.qp, n * NQ, C, s);
+      qin = W.qp;
     }
-    gemmf(s, qin, C, L.self.q, m_qh_, C, n * NQ, ACT_NONE);
-    gemmf(s, qin, C, L.self.k, m_kh_, C, n * NQ, ACT_NONE);
-    gemmf(s, m_q_, C, L.self.v, m_vh_, C, n * NQ, ACT_NONE);
-    attn(m_qh_, m_kh_, m_vh_, m_att_, NQ, NQ, C);
+    gemmf(s, qin, C, L.self.q, W.qh, C, n * NQ, ACT_NONE);
+    gemmf(s, qin, C, L.self.k, W.kh, C, n * NQ, ACT_NONE);
+    gemmf(s, W.q, C, L.self.v, W.vh, C, n * NQ, ACT_NONE);
+    attn(W.qh, W.kh, W.vh, W.att, NQ, NQ, C);
     if (i == 0)
-      gemmf(s, m_att_, C, L.self.o, m_q_, C, n * NQ, ACT_NONE);
+      gemmf(s, W.att, C, L.self.o, W.q, C, n * NQ, ACT_NONE);
     else
-      gemmf(s, m_att_, C, L.self.o, m_q_, C, n * NQ, ACT_NONE, m_q_, C);
-    lnf(m_q_, L.n1, n * NQ);
+      gemmf(s, W.att, C, L.self.o, W.q, C, n * NQ, ACT_NONE, W.q, C);
+    lnf(W.q, L.n1, n * NQ);
     // (2) tokens attend to the image
     token_to_image(L.t2i);
-    lnf(m_q_, L.n2, n * NQ);
+    lnf(W.q, L.n2, n * NQ);
     // (3) MLP on the tokens
-    gemmf(s, m_q_, C, L.lin1, m_mlp_, c.dec_mlp, n * NQ, ACT_RELU);
-    gemmf(s, m_mlp_, c.dec_mlp, L.lin2, m_q_, C, n * NQ, ACT_NONE, m_q_, C);
-    lnf(m_q_, L.n3, n * NQ);
+    gemmf(s, W.q, C, L.lin1, W.mlp, c.dec_mlp, n * NQ, ACT_RELU);
+    gemmf(s, W.mlp, c.dec_mlp, L.lin2, W.q, C, n * NQ, ACT_NONE, W.q, C);
+    lnf(W.q, L.n3, n * NQ);
     // (4) image attends to the tokens: q = keys + key_pe, k = queries + query_pe, v = queries
-    launch_add_rows(m_q_, m_tokens_, n * NQ, m_qp_, n * NQ, C, s);
+    launch_add_rows(W.q, W.tokens, n * NQ, W.qp, n * NQ, C, s);
     launch_add_rows(m_keys_, dense_pe_, NK, m_kp_, n * NK, C, s);
     gemmf(s, m_kp_, C, L.i2t.q, m_bigq_, Ci, n * NK, ACT_NONE);
-    gemmf(s, m_qp_, C, L.i2t.k, m_kh_, Ci, n * NQ, ACT_NONE);
-    gemmf(s, m_q_, C, L.i2t.v, m_vh_, Ci, n * NQ, ACT_NONE);
-    attn(m_bigq_, m_kh_, m_vh_, m_bigatt_, NK, NQ, Ci);
+    gemmf(s, W.qp, C, L.i2t.k, W.kh, Ci, n * NQ, ACT_NONE);
+    gemmf(s, W.q, C, L.i2t.v, W.vh, Ci, n * NQ, ACT_NONE);
+    attn(m_bigq_, W.kh, W.vh, m_bigatt_, NK, NQ, Ci);
     gemmf(s, m_bigatt_, Ci, L.i2t.o, m_keys_, C, n * NK, ACT_NONE, m_keys_, C);
     lnf(m_keys_, L.n4, n * NK);
   }
   token_to_image(dec_final_);
-  lnf(m_q_, dec_norm_final_, n * NQ);
+  lnf(W.q, dec_norm_final_, n * NQ);
 
   // ---- upscaler: ConvT(k2s2) = GEMM + un-shuffle, LayerNorm2d + GELU, ConvT, GELU, hyper product ----
   gemmf(s, m_keys_, C, up1_, m_up0_, C, n * NK, ACT_NONE);
@@ -2449,7 +2552,7 @@ void Model<T, TS>::mask_decoder(hipStream_t s, const float* image_emb, const flo
     GemmArgs a;
     const int in = hyper_[j].k, outn = hyper_[j].n;
     if (j == 0) {
-      a.A = m_q_ + C; a.lda = NQ * C; a.sA = C;
+      a.A = W.q + C; a.lda = NQ * C; a.sA = C;
     } else {
       a.A = j == 1 ? m_hy0_ : m_hy1_; a.lda = in; a.sA = (int64_t)n * in;
     }
@@ -2465,7 +2568,7 @@ void Model<T, TS>::mask_decoder(hipStream_t s, const float* image_emb, const flo
   }
   launch_upscale2_masks(m_up2_, m_hyper_, n, nt, 2 * g, C / 8, masks4 ? masks4 : m_masks_, s);
   if (iou) {
-    gemmf(s, m_q_, NQ * C, iou_head_[0], m_hy0_, C, n, ACT_RELU);
+    gemmf(s, W.q, NQ * C, iou_head_[0], m_hy0_, C, n, ACT_RELU);
     gemmf(s, m_hy0_, C, iou_head_[1], m_hy1_, C, n, ACT_RELU);
     // last layer has N = nt (not a multiple of 4 in K? K = C, fine)
     gemmf(s, m_hy1_, C, iou_head_[2], iou, nt, n, ACT_NONE);
@@ -2485,6 +2588,90 @@ void Model<T, TS>::mask_decode(hipStream_t s, const float* image_emb, const floa
     launch_postprocess(m, (int64_t)cfg.num_mask_tokens * L * L, n, L, L, cfg.sam_img, resized_hw[0], resized_hw[1],
                        orig_hw[0], orig_hw[1], out_masks, s);
   }
+}
+
+// every refusal of the prompted entries happens here or before: nothing is queued behind a throw
+template <typename T, typename TS>
+void Model<T, TS>::check_prompts(const char* who, const anyref_spatial_prompts* sp) const {
+  const std::string w(who);
+  if (sp_maxP_ == 0) throw std::runtime_error(w + ": spatial prompts are not reserved (anyref_prompt_reserve first)");
+  if (!sp) return;
+  if (sp->n_points < 0 || sp->n_points > sp_maxP_)
+    throw std::runtime_error(w + ": n_points " + std::to_string(sp->n_points) + " outside [0, max_points = " +
+                             std::to_string(sp_maxP_) + "]");
+  if (sp->n_points > 0 && (!sp->points || !sp->labels)) throw std::runtime_error(w + ": points given without labels (or labels without points)");
+  if (sp->multimask != 0 && sp->multimask != 1) throw std::runtime_error(w + ": multimask must be 0 or 1");
+  if (sp->multimask && cfg.num_mask_tokens < 4) throw std::runtime_error(w + ": multimask needs 4 mask tokens");
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::mask_decode_prompted(hipStream_t s, const float* image_emb, const float* pred_emb, int n,
+                                    const anyref_spatial_prompts* sp, float* masks4, float* iou, const int32_t* resized_hw,
+                                    const int32_t* orig_hw, float* out_masks) {
+  HIP_TRY(hipSetDevice(device_));
+  check_prompts("anyref_mask_decode_prompted", sp);
+  if (!image_emb) throw std::runtime_error("anyref_mask_decode_prompted: image_emb is NULL");
+  if (out_masks && (!resized_hw || !orig_hw)) throw std::runtime_error("anyref_mask_decode_prompted: out_masks without sizes");
+  if (n > cfg.max_seg) throw std::runtime_error("more prompts than max_seg");
+  if (n <= 0) return;
+  const anyref_spatial_prompts none{};
+  const anyref_spatial_prompts& p = sp ? *sp : none;
+  mask_decoder(s, image_emb, pred_emb, n, masks4, iou, &p);
+  if (out_masks) {
+    const int L = 4 * sam_g_, nt = cfg.num_mask_tokens;
+    const float* m = masks4 ? masks4 : m_masks_;
+    if (!p.multimask) {
+      launch_postprocess(m, (int64_t)nt * L * L, n, L, L, cfg.sam_img, resized_hw[0], resized_hw[1], orig_hw[0], orig_hw[1],
+                         out_masks, s);
+    } else {  // tokens 1..3 of every prompt (mask_decoder.py:106-112)
+      const int64_t hw = (int64_t)orig_hw[0] * orig_hw[1];
+      for (int i = 0; i < n; ++i)
+        launch_postprocess(m + ((int64_t)i * nt + 1) * L * L, (int64_t)L * L, 3, L, L, cfg.sam_img, resized_hw[0], resized_hw[1],
+                           orig_hw[0], orig_hw[1], out_masks + (int64_t)i * 3 * hw, s);
+    }
+  }
+}
+
+template <typename T, typename TS>
+const ModelBase::RefineRow& Model<T, TS>::refine_row(const char* who, int row, int seg) const {
+  const std::string w(who);
+  if (refine_rows_.empty()) {
+    if (refine_lost_by_) throw std::runtime_error(std::string("refine lost: ended by ") + refine_lost_by_);
+    throw std::runtime_error(w + ": no generating call on this handle yet");
+  }
+  if (row < 0 || row >= (int)refine_rows_.size()) throw std::runtime_error(w + ": row outside the last call");
+  const RefineRow& r = refine_rows_[row];
+  if (seg < 0 || seg >= r.n) throw std::runtime_error(w + ": seg outside the row's masks of the last call");
+  return r;
+}
+
+template <typename T, typename TS>
+void Model<T, TS>::refine_embedding(hipStream_t s, int row, int seg, float* out) {
+  HIP_TRY(hipSetDevice(device_));
+  if (!out) throw std::runtime_error("anyref_refine_embedding: out is NULL");
+  const RefineRow& r = refine_row("anyref_refine_embedding", row, seg);
+  HIP_TRY(hipMemcpyAsync(out, pred_emb_ + (size_t)(r.pred_row0 + seg) * cfg.out_dim, (size_t)cfg.out_dim * 4,
+                         hipMemcpyDeviceToDevice, s));
+}
+
+// mask `seg` of row `row` of the last generating call, decoded again with spatial prompts beside its [SEG] embedding: reads
+// sam_emb_ / pred_emb_, writes the decoder's workspaces and the caller's buffers only
+template <typename T, typename TS>
+void Model<T, TS>::refine_masks(hipStream_t s, int row, int seg, const anyref_spatial_prompts* sp, float* out_low, float* iou,
+                            float* out_masks) {
+  HIP_TRY(hipSetDevice(device_));
+  check_prompts("anyref_refine_masks", sp);
+  const RefineRow& r = refine_row("anyref_refine_masks", row, seg);
+  const anyref_config& c = cfg;
+  const int NK = sam_g_ * sam_g_, C = c.sam_out_chans, L = 4 * sam_g_;
+  const anyref_spatial_prompts none{};
+  const anyref_spatial_prompts& p = sp ? *sp : none;
+  mask_decoder(s, sam_emb_ + (size_t)r.emb_slot * NK * C, pred_emb_ + (size_t)(r.pred_row0 + seg) * c.out_dim, 1, nullptr, iou, &p);
+  const int k = p.multimask ? 3 : 1;
+  const float* m = m_masks_ + (p.multimask ? (size_t)L * L : 0);
+  if (out_low) HIP_TRY(hipMemcpyAsync(out_low, m, (size_t)k * L * L * 4, hipMemcpyDeviceToDevice, s));
+  if (out_masks)
+    launch_postprocess(m, (int64_t)L * L, k, L, L, c.sam_img, r.rhw[0], r.rhw[1], r.ohw[0], r.ohw[1], out_masks, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2660,6 +2847,25 @@ void Model<T, TS>::run_tail(hipStream_t s, const float* sam_images, int B, const
     throw std::runtime_error("packed masks capacity too small: the call's masks take " + std::to_string(pack_total) +
                              " words, cap_words is " + std::to_string(pack_cur_cap_));
   if (done > nseg) throw std::runtime_error("internal: more early [SEG] masks than [SEG] tokens");
+  if (refine_arm_) {
+    // what anyref_refine_masks needs of this call: mask (b, j) came from row r0 + j of pred_emb_ -- the early path's slot j of
+    // a one-image call is that row too -- and from image-embedding slot b, or slot 0 behind an open session
+    refine_arm_ = false;
+    refine_lost_by_ = nullptr;
+    refine_rows_.assign(B, RefineRow());
+    int r0 = 0;
+    for (int b = 0; b < B; ++b) {
+      RefineRow& r = refine_rows_[b];
+      r.pred_row0 = r0;
+      r.n = out_nseg[b];
+      r.emb_slot = one_image ? 0 : b;
+      for (int i = 0; i < 2; ++i) {
+        r.rhw[i] = resized_hw[2 * b + i];
+        r.ohw[i] = orig_hw[2 * b + i];
+      }
+      r0 += out_nseg[b];
+    }
+  }
   // mask reports: the records of every row -- the early ones too, `s` has joined their stream -- go to the pinned image
   // behind the last report; the read (mask_reports) waits for rep_ev_, the call gains no synchronisation
   auto reports_done = [&]() {

@@ -6,6 +6,7 @@
 #include "../../include/anyref_hip_ops.h"
 #include "kernels.h"
 #include "mask_report.h"
+#include "prompt_encode.h"
 
 using namespace anyref;
 
@@ -689,6 +690,25 @@ int anyref_op_dense_pe(void* stream, const float* gauss, int g, int F, float* ou
 
 int anyref_op_build_tokens(void* stream, const float* out_tokens, int n_out, const float* pred, int n, int C, float* tokens) {
   OP_GUARD(launch_build_tokens(out_tokens, n_out, pred, n, C, tokens, (hipStream_t)stream));
+}
+
+int anyref_op_prompt_tokens(void* stream, const float* out_tokens, int n_out, const float* points, const int32_t* labels, int P,
+                            const float* boxes, const float* text, const float* gauss, const float* emb5, int n, int C, int S,
+                            float* tokens, int max_wg) {
+  OP_GUARD(launch_prompt_tokens(out_tokens, n_out, points, labels, P, boxes, text, gauss, emb5, n, C, S, tokens,
+                                (hipStream_t)stream, max_wg));
+}
+
+int anyref_op_mask_prompt_embed(void* stream, const float* mask, const float* image_emb, const float* w1, const float* b1,
+                                const float* ln1_g, const float* ln1_b, const float* w2, const float* b2, const float* ln2_g,
+                                const float* ln2_b, const float* w3, const float* b3, int n, int g, int C, int c1, int c2,
+                                float* keys, int max_wg) {
+  OP_GUARD({
+    MaskDownW W;
+    W.w1 = w1; W.b1 = b1; W.g1 = ln1_g; W.be1 = ln1_b; W.w2 = w2; W.b2 = b2; W.g2 = ln2_g; W.be2 = ln2_b; W.w3 = w3; W.b3 = b3;
+    W.c1 = c1; W.c2 = c2;
+    launch_mask_prompt_embed(mask, image_emb, W, n, g, C, keys, (hipStream_t)stream, max_wg);
+  });
 }
 
 int anyref_op_add_rows(void* stream, const float* a, const float* b, int bmod, float* out, int M, int D) {

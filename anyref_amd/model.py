@@ -70,7 +70,7 @@ _NEEDS_HANDLE = frozenset({
     "seg_tail", "postprocess", "audio_encode", "device_bytes", "inexact_weights", "set_overlap", "set_early_tail", "set_graphs", "profile_enable", "profile_read",
     "stamps_enable", "stamps_read", "set_side_share", "llm_extend", "set_draft", "draft_stats", "image_session", "session_pool",
     "set_rephrase_paths", "early_masks_done", "load_adapter", "set_adapter", "set_token_scores", "last_token_scores",
-    "set_mask_reports", "last_mask_reports"})
+    "set_mask_reports", "last_mask_reports", "set_spatial_prompts", "refine", "refine_embedding"})
 
 # the tensors an adapter's `modules_to_save` may carry (train.py:375-387) and anyref_update_weight replaces on a live handle
 _SAVED_EXACT = ("model.embed_tokens.weight", "lm_head.weight", "model.text_hidden_fcs.0.0.weight",
@@ -143,6 +143,8 @@ class AnyRefForCausalLM:
         self._reports_packed = False                 # ... with a packed-mask buffer armed for every mask-producing call
         self._reports_call = None                    # (heights, widths, packed buffer) of the last such call, read on demand
         self._reports_many = None                    # generate_many: the entries of its calls, in the caller's item order
+        self._sp_max = 0                             # set_spatial_prompts
+        self._refine_ctx = None                      # low-res logits and sizes of the last generating call (refine)
         # `from_pretrained` flow: weights are gathered on the host first (base checkpoint, CLIP tower, SAM file,
         # token-row resize, LoRA merge all happen BEFORE `.cuda()` in the callers) and go to HBM in one build
         self._host_sd: Optional[Dict[str, torch.Tensor]] = {} if defer else None
@@ -877,10 +879,19 @@ class AnyRefForCausalLM:
         self._check(self.lib.anyref_sam_encode(self.h, self._stream(), _ptr(x), B, _ptr(out)), "sam_encode")
         return out.view(B, g, g, -1).permute(0, 3, 1, 2)
 
-    def mask_decode(self, image_embedding: torch.Tensor, pred_embeddings: torch.Tensor, resized_size=None,
-                    original_size=None):
+    def mask_decode(self, image_embedding: torch.Tensor, pred_embeddings: Optional[torch.Tensor], resized_size=None,
+                    original_size=None, points=None, point_labels=None, boxes=None, mask_input=None,
+                    multimask_output: bool = False):
         """image_embedding [256,g,g] or [1,256,g,g]; pred_embeddings [n,256] ->
-        dict(masks4 [n,4,4g,4g], iou [n,4], masks [n,H,W] if sizes given)."""
+        dict(masks4 [n,4,4g,4g], iou [n,4], masks [n,H,W] if sizes given).
+
+        With any of `points` [n,P,2] + `point_labels` [n,P], `boxes` [n,4], `mask_input` [n,4g,4g], `multimask_output`, or
+        with `pred_embeddings=None` (a pure SAM prompt): the prompted path (`set_spatial_prompts` first).  Coordinates are in
+        the SAM input frame, as for the reference's `predict_torch`.  It adds `low_res` [n,k,4g,4g] and `best` [n] to the
+        dict; with `multimask_output`, `masks` is [n,3,H,W] (mask tokens 1..3)."""
+        if pred_embeddings is None or multimask_output or any(a is not None for a in (points, point_labels, boxes, mask_input)):
+            return self._mask_decode_prompted(image_embedding, pred_embeddings, resized_size, original_size, points,
+                                              point_labels, boxes, mask_input, multimask_output)
         g, Cc = self.cfg.sam.grid, self.cfg.sam.out_chans
         e = image_embedding.reshape(Cc, g * g).t().to(self.device, torch.float32).contiguous()
         p = pred_embeddings.to(self.device, torch.float32).reshape(-1, self.cfg.out_dim).contiguous()
@@ -895,6 +906,115 @@ class AnyRefForCausalLM:
         self._check(self.lib.anyref_mask_decode(self.h, self._stream(), _ptr(e), _ptr(p), n, _ptr(m4), _ptr(iou),
                                                 rs, os_, _ptr(out)), "mask_decode")
         return dict(masks4=m4, iou=iou, masks=out)
+
+    # ---- SAM spatial prompts beside [SEG] -----------------------------------
+    def set_spatial_prompts(self, max_points: int = 8):
+        """Reserve the prompted decoder path (`anyref_prompt_reserve`): points, boxes and low-res masks beside the [SEG]
+        embedding in `mask_decode(...)` and `refine(...)`.  Needs the spatial weights of SAM's prompt encoder in the state
+        dict (`anyref_amd.prompts.SPATIAL_NAMES`).  0 frees the workspaces.  While reserved, the generating calls keep their
+        low-res logits for `refine(..., mask_input=True)`."""
+        self._check(self.lib.anyref_prompt_reserve(self.h, int(max_points)), "prompt_reserve")
+        self._sp_max = int(max_points)
+        self._refine_ctx = None
+
+    def _spatial(self, n, points, labels, boxes, mask_input, multimask):
+        """-> (anyref_spatial_prompts, the device tensors it points to)"""
+        L = 4 * self.cfg.sam.grid
+        sp, keep = _lib.SpatialPrompts(), []
+
+        def dev(t, dtype, shape):
+            t = torch.as_tensor(t).to(self.device, dtype).reshape(shape).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+        if (points is None) != (labels is None):
+            raise ValueError("points and point labels come together")
+        if points is not None:
+            lab = torch.as_tensor(labels).reshape(n, -1)
+            if not bool(((lab == -1) | (lab == 0) | (lab == 1)).all()):
+                raise ValueError("point labels are 1 (foreground), 0 (background) or -1 (not a point)")
+            sp.n_points = lab.shape[1]
+            sp.points, sp.labels = dev(points, torch.float32, (n, sp.n_points, 2)), dev(lab, torch.int32, (n, sp.n_points))
+        if boxes is not None:
+            sp.boxes = dev(boxes, torch.float32, (n, 4))
+        if mask_input is not None:
+            sp.mask_input = dev(mask_input, torch.float32, (n, L, L))
+        sp.multimask = int(bool(multimask))
+        return sp, keep
+
+    def _mask_decode_prompted(self, image_embedding, pred_embeddings, resized_size, original_size, points, point_labels, boxes,
+                              mask_input, multimask_output):
+        g, Cc, L = self.cfg.sam.grid, self.cfg.sam.out_chans, 4 * self.cfg.sam.grid
+        e = image_embedding.reshape(Cc, g * g).t().to(self.device, torch.float32).contiguous()
+        p = None if pred_embeddings is None else \
+            pred_embeddings.to(self.device, torch.float32).reshape(-1, self.cfg.out_dim).contiguous()
+        if p is not None:                       # the prompt count, as the reference's _get_batch_size finds it
+            n = p.shape[0]
+        elif points is not None:
+            n = torch.as_tensor(points).reshape(-1, torch.as_tensor(point_labels).shape[-1], 2).shape[0]
+        elif boxes is not None:
+            n = torch.as_tensor(boxes).reshape(-1, 4).shape[0]
+        else:
+            n = 1 if mask_input is None else torch.as_tensor(mask_input).reshape(-1, L, L).shape[0]
+        nt, k = self.cfg.sam.num_mask_tokens, 3 if multimask_output else 1
+        sp, keep = self._spatial(n, points, point_labels, boxes, mask_input, multimask_output)
+        m4 = torch.empty(n, nt, L, L, device=self.device, dtype=torch.float32)
+        iou = torch.empty(n, nt, device=self.device, dtype=torch.float32)
+        out = rs = os_ = None
+        if original_size is not None:
+            out = torch.empty(n, k, int(original_size[0]), int(original_size[1]), device=self.device, dtype=torch.float32)
+            rs = (C.c_int32 * 2)(int(resized_size[0]), int(resized_size[1]))
+            os_ = (C.c_int32 * 2)(int(original_size[0]), int(original_size[1]))
+        self._check(self.lib.anyref_mask_decode_prompted(self.h, self._stream(), _ptr(e), _ptr(p), n, C.byref(sp), _ptr(m4),
+                                                         _ptr(iou), rs, os_, _ptr(out)), "mask_decode_prompted")
+        from .prompts import pick
+        tokens, best = pick(iou, multimask_output)
+        if out is not None and not multimask_output:
+            out = out[:, 0]
+        return dict(masks4=m4, iou=iou, masks=out, low_res=m4[:, tokens], best=best)
+
+    def refine_embedding(self, row: int, seg: int) -> torch.Tensor:
+        """the [SEG] prompt embedding [out_dim] that `refine(row, seg)` starts from (`anyref_refine_embedding`)"""
+        out = torch.empty(self.cfg.out_dim, device=self.device, dtype=torch.float32)
+        self._check(self.lib.anyref_refine_embedding(self.h, self._stream(), int(row), int(seg), _ptr(out)), "refine_embedding")
+        return out
+
+    def _refine_keep(self, out_low, resized, height, width):
+        """after a generating call: what `refine` needs of it on the host"""
+        self._refine_ctx = dict(low=out_low, resized=[(int(a), int(b)) for a, b in resized],
+                                orig=[(int(h), int(w)) for h, w in zip(height, width)]) if self._sp_max else None
+
+    @torch.no_grad()
+    def refine(self, row: int, seg: int, points=None, labels=None, box=None, mask_input=None, multimask_output: bool = False):
+        """Decode mask `seg` of row `row` of the last `generate` / session / pooled call again, with spatial prompts ADDED to
+        that [SEG]'s own embedding (`anyref_refine_masks`).  Coordinates are in ORIGINAL image pixels, as for the reference's
+        `SamPredictor.predict`: points [P, 2] (x, y) with labels [P] in {1, 0, -1}, box [4] (x0 y0 x1 y1).  `mask_input`: low-res
+        logits [4g, 4g], or True for the ones this mask had.  -> dict(masks [k, H, W], low_res [k, 4g, 4g], iou [k], best),
+        k = 3 with `multimask_output` (mask tokens 1..3, best = argmax of their predicted IoU), else 1."""
+        from .prompts import pick, to_input_frame
+        ctx = getattr(self, "_refine_ctx", None)
+        if not self._sp_max:
+            raise RuntimeError("refine: spatial prompts are not reserved (model.set_spatial_prompts() first)")
+        if ctx is None or not (0 <= int(row) < len(ctx["orig"])):
+            raise RuntimeError("refine: row outside the last generating call (or none since set_spatial_prompts)")
+        row, seg = int(row), int(seg)
+        rhw, ohw = ctx["resized"][row], ctx["orig"][row]
+        if points is not None:
+            points = to_input_frame(torch.as_tensor(points, dtype=torch.float64).reshape(-1, 2), ohw, rhw)
+        if box is not None:
+            box = to_input_frame(torch.as_tensor(box, dtype=torch.float64).reshape(2, 2), ohw, rhw).reshape(4)
+        if mask_input is True:
+            if not (0 <= seg < ctx["low"].shape[1]):
+                raise RuntimeError("refine: seg outside the row's masks of the last call")
+            mask_input = ctx["low"][row, seg]
+        L, nt, k = 4 * self.cfg.sam.grid, self.cfg.sam.num_mask_tokens, 3 if multimask_output else 1
+        sp, keep = self._spatial(1, points, labels, box, mask_input, multimask_output)
+        low = torch.empty(k, L, L, device=self.device, dtype=torch.float32)
+        iou = torch.empty(nt, device=self.device, dtype=torch.float32)
+        out = torch.empty(k, ohw[0], ohw[1], device=self.device, dtype=torch.float32)
+        self._check(self.lib.anyref_refine_masks(self.h, self._stream(), row, seg, C.byref(sp), _ptr(low), _ptr(iou), _ptr(out)),
+                    "refine_masks")
+        tokens, best = pick(iou, multimask_output)
+        return dict(masks=out, low_res=low, iou=iou[tokens], best=int(best))
 
     def llm_forward(self, embeds: torch.Tensor, lens: Optional[Sequence[int]] = None, want_logits: bool = False,
                     attn_q: Optional[Sequence[int]] = None):
@@ -992,10 +1112,10 @@ class AnyRefForCausalLM:
         cap = sum(self.max_seg * h * w for h, w in zip(height, width))
         out_masks = torch.empty(cap, device=self.device, dtype=torch.float32)
         out_low = hid = None
-        if _return_extras:       # low-res logits (what a DP driver all-gathers) and, unless "low", the hidden states
+        if _return_extras or self._sp_max:   # low-res logits (what a DP driver all-gathers; what refine(mask_input=True) feeds back)
             L = 4 * self.cfg.sam.grid
             out_low = torch.zeros(B, self.max_seg, L, L, device=self.device, dtype=torch.float32)
-            if _return_extras != "low":
+            if _return_extras and _return_extras != "low":   # ... and, unless "low", the hidden states
                 hid = torch.empty(B, self.cfg.llm.max_seq, self.cfg.llm.dim, device=self.device, dtype=torch.float32)
         eos = self.config.eos_token_id if self.config.eos_token_id is not None else -1
         if drafts is not None and any(drafts):
@@ -1007,6 +1127,7 @@ class AnyRefForCausalLM:
             _ptr(out_nseg), _ptr(out_masks), cap, _ptr(offs), _ptr(out_low), _ptr(hid)), "generate")
         self._generated(B, max_new_tokens)
         self._masks_made(pending)
+        self._refine_keep(out_low, sam_resized_sizes, height, width)
         if self._draft_policy == "last":
             self._last_answers = [out_ids[b, int(lens[b]): int(out_lens[b])].tolist() for b in range(B)]
         res = self._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width)
@@ -1203,6 +1324,7 @@ class ImageSession:
         if len(rs) != 2 or len(hh) != 1 or len(ww) != 1:
             raise ValueError("an image session holds exactly one image: one (h, w) resized size, one height, one width")
         self.height, self.width = hh[0], ww[0]
+        self.resized = (rs[0], rs[1])
         rs_t = torch.tensor(rs, dtype=torch.int32)
         os_t = torch.tensor([self.height, self.width], dtype=torch.int32)
         pre = torch.tensor(self.prefix, dtype=torch.long)
@@ -1221,6 +1343,10 @@ class ImageSession:
         if self.open and self.model.h:
             self.model._check(self.model.lib.anyref_session_close(self.model.h), "session_close")
         self.open = False
+
+    def refine(self, query: int, seg: int, **kw):
+        """`model.refine` for mask `seg` of query `query` of this session's last `generate`; the session stays open"""
+        return self.model.refine(query, seg, **kw)
 
     @torch.no_grad()
     def generate(self, input_ids, audios=None, ref_images=None, max_new_tokens=128, attention_masks=None, draft_ids=None,
@@ -1259,10 +1385,10 @@ class ImageSession:
         cap = Q * m.max_seg * self.height * self.width
         out_masks = torch.empty(cap, device=m.device, dtype=torch.float32)
         out_low = hid = None
-        if _return_extras:
+        if _return_extras or m._sp_max:
             L = 4 * m.cfg.sam.grid
             out_low = torch.zeros(Q, m.max_seg, L, L, device=m.device, dtype=torch.float32)
-            if _return_extras != "low":
+            if _return_extras and _return_extras != "low":
                 hid = torch.empty(Q, m.cfg.llm.max_seq, m.cfg.llm.dim, device=m.device, dtype=torch.float32)
         eos = m.config.eos_token_id if m.config.eos_token_id is not None else -1
         if draft_ids is not None:
@@ -1276,6 +1402,7 @@ class ImageSession:
             "session_generate")
         m._generated(Q, max_new_tokens)
         m._masks_made(pending)
+        m._refine_keep(out_low, [self.resized] * Q, height, width)
         res = m._result(out_ids, out_lens, out_nseg, offs, out_masks, height, width, per_row=True)
         if _return_extras:
             return res, dict(out_lens=out_lens, nseg=out_nseg, low_res=out_low, hidden=hid, **m.draft_stats(Q))
@@ -1350,6 +1477,7 @@ class SessionPool:
             sess.close()                          # the slot holds it now; the working buffers are free for any other call
         self._held = [None] * m.max_batch
         ps = PooledSession(self, key, slot, self.table.gens[slot], sess.prefix, sess.height, sess.width)
+        ps.resized = sess.resized
         self._sessions[key] = ps
         return ps
 
@@ -1428,10 +1556,10 @@ class SessionPool:
         cap = sum(m.max_seg * h * w for h, w in zip(height, width))
         out_masks = torch.empty(cap, device=m.device, dtype=torch.float32)
         out_low = hid = None
-        if _return_extras:
+        if _return_extras or m._sp_max:
             L = 4 * m.cfg.sam.grid
             out_low = torch.zeros(Q, m.max_seg, L, L, device=m.device, dtype=torch.float32)
-            if _return_extras != "low":
+            if _return_extras and _return_extras != "low":
                 hid = torch.empty(Q, m.cfg.llm.max_seq, m.cfg.llm.dim, device=m.device, dtype=torch.float32)
         eos = m.config.eos_token_id if m.config.eos_token_id is not None else -1
         if draft_ids is not None:
@@ -1445,6 +1573,7 @@ class SessionPool:
             _ptr(out_low), _ptr(hid)), "session_generate_pooled")
         m._generated(Q, max_new_tokens)
         m._masks_made(pending)
+        m._refine_keep(out_low, [ps.resized for ps in sessions], height, width)
         for b, ps in enumerate(sessions):
             self.table.touch(ps.key)
             self._held[b] = (ps.slot, ps.gen)

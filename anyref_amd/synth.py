@@ -217,3 +217,44 @@ def synth_state_dict(cfg: AnyRefConfig, seed: int = 0, scale: float = 0.02, devi
             t = t.to(torch.bfloat16).to(torch.float32)
         out[name] = t.to(dtype)
     return out
+
+
+def prompt_weight_shapes(cfg: AnyRefConfig, mask_in_chans: int = 16) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
+    """(name, shape, kind) of SAM's spatial-prompt weights (prompt_encoder.py:43-65): the optional half of the prompt
+    encoder, which `weight_shapes` leaves out."""
+    C, c2 = cfg.sam.out_chans, mask_in_chans
+    c1 = c2 // 4
+    p = SAM_PREFIX + "prompt_encoder."
+    for i in range(4):
+        yield p + f"point_embeddings.{i}.weight", (1, C), "e"
+    yield p + "not_a_point_embed.weight", (1, C), "e"
+    for i, (co, ci, k) in ((0, (c1, 1, 2)), (3, (c2, c1, 2)), (6, (C, c2, 1))):
+        yield p + f"mask_downscaling.{i}.weight", (co, ci, k, k), "w"
+        yield p + f"mask_downscaling.{i}.bias", (co,), "b"
+    for i, ch in ((1, c1), (4, c2)):
+        yield p + f"mask_downscaling.{i}.weight", (ch,), "g"
+        yield p + f"mask_downscaling.{i}.bias", (ch,), "b"
+
+
+def synth_prompt_weights(cfg: AnyRefConfig, seed: int = 0, mask_in_chans: int = 16, device="cpu",
+                         round_bf16: bool = True) -> Dict[str, torch.Tensor]:
+    """Seeded spatial-prompt weights, from a generator of their own: `synth_state_dict`'s draw order does not move (the
+    committed fixtures carry checksums of it).  Embeddings ~ N(0, 0.5^2), convolutions ~ N(0, 1 / fan_in), biases
+    ~ N(0, 0.05^2), norm gains 1 + N(0, 0.1^2) -- every term of the rule is visible in the output."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed + 7919)
+    out: Dict[str, torch.Tensor] = {}
+    for name, shape, kind in prompt_weight_shapes(cfg, mask_in_chans):
+        t = torch.randn(shape, generator=gen, device=device, dtype=torch.float32)
+        if kind == "e":
+            t = t * 0.5
+        elif kind == "w":
+            t = t / _fan_in(name, shape) ** 0.5
+        elif kind == "b":
+            t = t * 0.05
+        elif kind == "g":
+            t = 1.0 + 0.1 * t
+        if round_bf16:
+            t = t.to(torch.bfloat16).to(torch.float32)
+        out[name] = t
+    return out

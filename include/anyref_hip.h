@@ -180,6 +180,43 @@ int anyref_sam_encode(anyref_handle* h, void* stream, const float* sam_images, i
 int anyref_mask_decode(anyref_handle* h, void* stream, const float* image_emb, const float* pred_emb,
                        int n, float* masks4, float* iou, const int32_t* resized_hw,
                        const int32_t* orig_hw, float* out_masks);
+
+/* ---- SAM spatial prompts beside [SEG] (prompt_encoder.py:78-186) ----
+ * Points, a box and a low-resolution mask join the [SEG] text embedding in one decoder pass.  Token order: points, one padding
+ * point (iff points are given and boxes are not), box corners, text.  The optional weights
+ * model.visual_model.prompt_encoder.{point_embeddings.{0..3}, not_a_point_embed, mask_downscaling.{0,1,3,4,6}} must have been
+ * handed to anyref_set_weight before anyref_finalize. */
+typedef struct anyref_spatial_prompts {
+  const float* points;     /* f32 dev [n,P,2] (x,y), SAM input frame; NULL iff n_points = 0 */
+  const int32_t* labels;   /* i32 dev [n,P]: 1 foreground, 0 background, -1 not a point */
+  int32_t n_points;        /* P, 0 .. max_points */
+  const float* boxes;      /* f32 dev [n,4] x0 y0 x1 y1, or NULL */
+  const float* mask_input; /* f32 dev [n,4g,4g] low-res logits, or NULL */
+  int32_t multimask;       /* 0: mask token 0;  1: tokens 1..3 */
+} anyref_spatial_prompts;
+/* After anyref_finalize: allocates the prompted path's workspaces for up to max_points points per prompt (counted in
+ * anyref_device_bytes).  Fails, naming the first missing tensor, if the spatial weights were not handed over.  0 frees them;
+ * the same value again changes nothing. */
+int anyref_prompt_reserve(anyref_handle* h, int max_points);
+/* anyref_mask_decode with spatial prompts.  pred_emb may be NULL: SamPredictor.predict on the given embedding.  sp NULL or
+ * with nothing set: the text prompt alone, bit-identical to anyref_mask_decode.  masks4 f32 [n,4,4g,4g] or NULL, iou f32
+ * [n,4] or NULL, out_masks f32 [n,k,H,W] or NULL, k = 1 (multimask 0: token 0) or 3 (tokens 1..3). */
+int anyref_mask_decode_prompted(anyref_handle* h, void* stream, const float* image_emb, const float* pred_emb, int n,
+                                const anyref_spatial_prompts* sp, float* masks4, float* iou, const int32_t* resized_hw,
+                                const int32_t* orig_hw, float* out_masks);
+/* Decodes mask `seg` of row `row` of the last anyref_generate / anyref_session_generate / anyref_session_generate_pooled
+ * again, with `sp` (n = 1, may be NULL) ADDED to that [SEG]'s own prompt embedding, on that row's image embedding and sizes.
+ * out_low f32 [k,4g,4g] dev or NULL, iou f32 [4] dev or NULL, out_masks f32 [k,H,W] dev or NULL.  Reads the working buffers
+ * and writes decoder workspaces only: an open session, pool slots and a pending draft stay usable, mask reports are not
+ * touched.  Refused with nothing queued when nothing is reserved, row / seg lie outside that call, n_points > max_points,
+ * points come without labels, or another entry has overwritten the embeddings since ("refine lost: ended by <entry>";
+ * anyref_refine_masks, anyref_mask_decode and anyref_mask_decode_prompted do not end it). */
+int anyref_refine_masks(anyref_handle* h, void* stream, int row, int seg, const anyref_spatial_prompts* sp, float* out_low,
+                        float* iou, float* out_masks);
+/* The prompt embedding of mask `seg` of row `row` of the last generating call, as anyref_refine_masks reads it: out f32
+ * [out_dim] dev.  With it, anyref_mask_decode_prompted on anyref_sam_encode's embedding reproduces a refine bit for bit.  Refused
+ * like anyref_refine_masks (it needs no reservation). */
+int anyref_refine_embedding(anyref_handle* h, void* stream, int row, int seg, float* out);
 /* LLaMA stack on given input embeddings (HF LlamaModel; call sites anyref.py:341-354).
  * embeds f32 [B,S,dim] dev, lens i32[B] host.  hidden f32 [B,S,dim] (post final norm),
  * logits f32 [B,S,vocab] or NULL, attn_row f32 [B,S] or NULL = head-mean last-layer attention of

@@ -288,6 +288,21 @@ int anyref_op_upscale2_masks(void* stream, const float* tmp, const float* hyper,
 int anyref_op_dense_pe(void* stream, const float* gauss, int g, int F, float* out);
 /* tokens f32 [n, n_out + 1, C]: rows 0 .. n_out-1 = out_tokens [n_out, C], row n_out = pred[i] */
 int anyref_op_build_tokens(void* stream, const float* out_tokens, int n_out, const float* pred, int n, int C, float* tokens);
+/* SAM spatial prompts (prompt_encode.hip).  tokens f32 [n, NQ, C], NQ = n_out + P + pad + 2 box + text, pad = (P > 0 and no
+ * boxes): out_tokens, then the points (PE + emb5[label] for label 0 / 1, emb5[4] alone for -1, the PE alone otherwise), the
+ * pad (emb5[4]), the box corners (PE + emb5[2], PE + emb5[3]), text[i].  points f32 [n,P,2] (x, y) in pixels of the S x S
+ * input frame, labels i32 [n,P], boxes f32 [n,4] or NULL, text f32 [n,C] or NULL, gauss f32 [2, C/2], emb5 f32 [5,C].
+ * C % 8 == 0.  max_wg > 0 caps the grid.  A refused call writes nothing */
+int anyref_op_prompt_tokens(void* stream, const float* out_tokens, int n_out, const float* points, const int32_t* labels, int P,
+                            const float* boxes, const float* text, const float* gauss, const float* emb5, int n, int C, int S,
+                            float* tokens, int max_wg);
+/* keys f32 [n, g*g, C] = image_emb [g*g, C] + mask_downscaling(mask f32 [n, 4g, 4g]) as NHWC: conv k2s2 w1 [c1,1,2,2] + b1,
+ * LayerNorm2d (ln1_g, ln1_b, eps 1e-6), GELU, conv k2s2 w2 [c2,c1,2,2] + b2, LayerNorm2d (ln2_g, ln2_b), GELU, conv 1x1
+ * w3 [C,c2] + b3.  c1 <= 8, c2 <= 32, C % 4 == 0, C <= 1024.  max_wg > 0 caps the grid.  A refused call writes nothing */
+int anyref_op_mask_prompt_embed(void* stream, const float* mask, const float* image_emb, const float* w1, const float* b1,
+                                const float* ln1_g, const float* ln1_b, const float* w2, const float* b2, const float* ln2_g,
+                                const float* ln2_b, const float* w3, const float* b3, int n, int g, int C, int c1, int c2,
+                                float* keys, int max_wg);
 /* out[m, :] = a[m, :] + b[m % bmod, :] and out[m, :] = a[m, :] + v[:]   (f32 [M, D]) */
 int anyref_op_add_rows(void* stream, const float* a, const float* b, int bmod, float* out, int M, int D);
 int anyref_op_add_vec(void* stream, const float* a, const float* v, float* out, int M, int D);
